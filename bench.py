@@ -23,10 +23,21 @@ bitmaps are all-gathered over RCCL on one communication stream, the only
 cross-GPU exchange the path has.
 
 Printed (rank 0, one JSON line): value = verifies/s of the whole job
-(kernel path, inputs resident), the single-batch latency and serial rate,
-end-to-end (host buffers, PCIe included), p50/p99 of a 150-validator commit
-through the host C-ABI, the roofline object and a CPU baseline (the C
-oracle "port" on the host's cores; the Go reference cannot be built here).
+(kernel path, inputs resident), ms_per_step and the roofline object.  A plain
+run does only that: setup, warmup, the timed steps, the line.  `--full` adds
+the measurements that take runs of their own: the single-batch latency and
+serial rate, end-to-end (host buffers, PCIe included), the strong-scaling
+legs, p50/p99 of a 150-validator commit through the host C-ABI, the kernels'
+own launch durations and a CPU baseline (the C oracle "port" on the host's
+cores; the Go reference cannot be built here); `--no-extras` and
+`--no-cpu-baseline` switch parts of `--full` off again.
+
+`--dump-outputs DIR` writes what the last timed step computed, as a caller
+of the path receives it: DIR/validity.npy, the step's validity vectors
+(float32, batches_per_step x batch; 1 = valid), and with N > 1 also
+DIR/gathered_validity.npy, the all-gathered vector of that launch (rank 0's
+copy).  The inputs are generated from fixed seeds, so two runs with the same
+arguments verify identical batches.
 """
 from __future__ import annotations
 
@@ -607,6 +618,25 @@ def _dominant_roofline(ktimes, ktimes_alone, K, n, args, peak, steps, pipeline, 
     return r
 
 
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: all files together
+DUMP_SEED = 0xD0
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array of `arrays` (name -> tensor) as
+    path/<name>.npy in float32, an equal share of DUMP_MAX_BYTES each; a
+    larger array is cut to a fixed sample (sorted indices from DUMP_SEED, the
+    same on every run) of its flattened entries."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_MAX_BYTES // (4 * max(1, len(arrays))) - 64  # float32 entries per file, less the .npy header
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        if a.size > share:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, size=share, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -619,8 +649,14 @@ def main():
     ap.add_argument("--inflight", type=int, default=4, help="launches in flight (streams)")
     ap.add_argument("--resident", type=int, default=64,
                     help="distinct C2 batches held in HBM per rank (a step's batches cycle through them)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip latency / end-to-end / C1 measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: latency / end-to-end / strong-scaling / C1 "
+                         "measurements, the kernels' own launch durations and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's validity vectors to DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip latency / end-to-end / strong-scaling / C1 measurements")
     ap.add_argument("--method", choices=["batch", "per-entry"], default="batch",
                     help="batch: random-linear-combination group check + per-entry fallback "
                          "(voi's BatchVerifier.Verify); per-entry: every signature verified singly")
@@ -635,6 +671,8 @@ def main():
                     help="CI only: run the launch / gather / timing control flow on the CPU (gloo) with a stub "
                          "engine that writes the known statuses; no GPU, no verification, not a measurement")
     args = ap.parse_args()
+    if not args.full:  # a plain run: setup, warmup, the timed steps, the result line
+        args.no_extras = args.no_cpu_baseline = True
     stub = args.cpu_stub
     t_main = time.perf_counter()
 
@@ -790,6 +828,14 @@ def main():
             if world > 1:  # the gathered vector holds every rank's copy of this launch
                 assert gathered[f].numel() == world * kk * n
         first += kk
+    if args.dump_outputs and rank == 0:
+        # the last timed step's vectors, still on its stream's buffer (the
+        # extras below reuse the buffers), and the gathered copy of that launch
+        f_last = (steps - 1) % F
+        outs = {"validity": d_valid[f_last][:sizes[-1] * n].view(sizes[-1], n)}
+        if world > 1:
+            outs["gathered_validity"] = gathered[f_last]
+        dump_outputs(args.dump_outputs, outs)
     build_digest = None if stub else (N.build_info() or {}).get("src_digest_compiled")
 
     def max_over_ranks(x):

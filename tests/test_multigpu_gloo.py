@@ -129,7 +129,7 @@ def test_bench_control_flow_world2():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), os.path.join(repo, "bench.py"), "--gpus", "2",
            "--steps", "7", "--warmup", "2", "--batch", "500", "--resident", "3", "--inflight", "2",
-           "--batches-per-step", "3", "--cpu-stub", "--strong-n", "4003"]
+           "--batches-per-step", "3", "--cpu-stub", "--strong-n", "4003", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=repo)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -151,3 +151,33 @@ def test_bench_control_flow_world2():
         assert s["exact_vector_on_every_rank"] is True
         assert s["kernel_only"]["verifies_per_s"] > 0 and s["end_to_end"]["verifies_per_s"] > 0
     assert r["end_to_end_verifies_per_s"] > 0 and "end_to_end_vs_headline" in r
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain bench.py run (no --full) times its steps and prints the line
+    without the extra measurements; --dump-outputs writes the last timed
+    step's validity vectors, the same from run to run (--cpu-stub engine:
+    the factory's known vectors)."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    from tendermint_amd.testing.factory import C2_VALID_KINDS, c2_kinds
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cmd = [sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--batch",
+           "300", "--resident", "4", "--inflight", "2", "--batches-per-step", "3", "--cpu-stub",
+           "--dump-outputs", str(tmp_path / "out")]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=repo)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    r = json.loads(lines[0])
+    assert r["steps"] == 5 and r["ms_per_step"] > 0 and r["value"] > 0 and r["cpu_baseline"] is None
+    for k in ("strong_1m", "end_to_end_verifies_per_s", "batch_latency_ms", "verify_commit_150_p50_ms"):
+        assert k not in r
+    assert os.listdir(tmp_path / "out") == ["validity.npy"]
+    got = np.load(tmp_path / "out" / "validity.npy")
+    assert got.dtype == np.float32 and got.shape == (3, 300)
+    # step 4 (the last of 5) verifies batches 12, 13, 14 of the cycle over 4 resident ones
+    want = [[float(k in C2_VALID_KINDS) for k in c2_kinds(300, 0xED25519 + j % 4)] for j in (12, 13, 14)]
+    assert np.array_equal(got, np.array(want, np.float32))

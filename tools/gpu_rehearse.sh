@@ -13,7 +13,7 @@ out=gpurun_out/rehearse_n$N
 mkdir -p "$out"
 t0=$(date +%s.%N)
 TMV_BENCH_BACKEND=gloo timeout -k 10 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" \
-  --master-addr 127.0.0.1 --master-port 29541 bench.py --gpus "$N" --steps 20 --warmup 5 \
+  --master-addr 127.0.0.1 --master-port 29541 bench.py --gpus "$N" --steps 20 --warmup 5 --full \
   --batches-per-step "$K" --resident "$R" > "$out/bench.log" 2>&1
 rc=$?
 t1=$(date +%s.%N)

@@ -15,7 +15,7 @@ run() {
   case $rc in 0) ;; *) echo "stopping after $name"; exit $rc;; esac
 }
 B="python3 tools/pmc_driver.py --launches 4"
-run trace 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o bench -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline
+run trace 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o bench -- python3 bench.py --steps 20 --warmup 5 --full --no-cpu-baseline
 run trace_ss 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_ss -o bench -- python3 bench.py --steps 48 --warmup 8 --no-cpu-baseline --no-extras
 run fetch 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -o fetch -- $B
 run write 120 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/write -o write -- $B

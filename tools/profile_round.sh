@@ -16,7 +16,7 @@ run() {
   return 0
 }
 B="python3 tools/pmc_driver.py --launches 4"
-run trace rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o bench -- python3 bench.py
+run trace rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o bench -- python3 bench.py --full
 run fetch rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -o fetch -- $B
 run write rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/write -o write -- $B
 run valu rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES --output-format csv -d $OUT/valu -o valu -- $B
