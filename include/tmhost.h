@@ -26,8 +26,11 @@
 extern "C" {
 #endif
 
-/* Key kinds: TMV_KIND_ED25519, TMV_KIND_SR25519; anything else is a key type
- * without batch support (e.g. secp256k1, crypto/batch/batch.go:13-20). */
+/* Key kinds: TMV_KIND_ED25519, TMV_KIND_SR25519 and TMV_KIND_SECP256K1 (33-byte
+ * compressed keys, crypto/secp256k1/secp256k1.go; verified signature by
+ * signature: no batch verifier, crypto/batch/batch.go:13-20); anything else
+ * is a key type this library cannot verify (every signature is wrong). */
+#define TMV_KIND_SECP256K1 3
 #define TMV_KIND_OTHER 255
 
 /* ---- crypto.BatchVerifier ---- */
@@ -150,7 +153,7 @@ typedef struct {
   uint32_t validator_address_len;
   const uint8_t *signature;
   uint32_t signature_len;
-  uint8_t key_kind; /* TMV_KIND_ED25519 / TMV_KIND_SR25519 */
+  uint8_t key_kind; /* TMV_KIND_ED25519 / TMV_KIND_SR25519 (secp256k1 votes: not verified here) */
   const uint8_t *pub_key;
   uint32_t pub_key_len;
 } tmv_vote_in;

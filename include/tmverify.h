@@ -98,6 +98,26 @@ int tmv_ed25519_verify_batch(tmv_ctx *ctx, const uint8_t *pk, const uint8_t *sig
 int tmv_ed25519_verify(tmv_ctx *ctx, const uint8_t *pk, const uint8_t *msg, size_t msg_len,
                        const uint8_t *sig, size_t sig_len);
 
+/* secp256k1 ECDSA batch verification, one verdict per entry.
+ * Replaces: crypto/secp256k1/secp256k1.go:206-226 PubKey.VerifySignature per
+ * entry (btcec ParsePubKey + Go's ecdsa.Verify over SHA-256(msg), lower-S
+ * signatures only).  Keys are the 33-byte compressed form, entry i at
+ * pk + 33*i -- the only size a validator set can hold (crypto/encoding/
+ * codec.go:49-78); sig is r || s, 64 bytes per entry.  valid_out[i] = 1/0: a
+ * key that does not parse, r or s out of range and an upper-S signature are
+ * 0, never an error.  Runs on the context's first device.  TMV_ERR_ARG for
+ * null pointers, msg_off[0] != 0, decreasing offsets, n > 2^26 or more than
+ * 2^30 message bytes. */
+int tmv_secp256k1_verify_batch(tmv_ctx *ctx, const uint8_t *pk, const uint8_t *sig, const uint8_t *msg,
+                               const uint32_t *msg_off, uint32_t n, uint8_t *valid_out);
+
+/* Single secp256k1 verification (secp256k1.go:206-226).  Returns 0 without
+ * touching the device when pk_len != 33 or sig_len != 64 (the reference
+ * returns false for a signature of another size; keys of another size cannot
+ * enter a validator set).  Returns 1/0 or <0. */
+int tmv_secp256k1_verify(tmv_ctx *ctx, const uint8_t *pk, size_t pk_len, const uint8_t *msg, size_t msg_len,
+                         const uint8_t *sig, size_t sig_len);
+
 /* sr25519 batch verification (Schnorrkel, empty signing context).
  * Replaces: crypto/sr25519/batch.go:23-47 Add + Verify.  status_out[i] is
  * 1 / 0 / TMV_SR_ADDERR_*; the return value is TMV_ALL_VALID only if every
@@ -162,8 +182,8 @@ int tmv_batch_stats(tmv_ctx *ctx, uint64_t *groups, uint64_t *groups_failed);
  * crypto/merkle/tree.go:11-27, over Validator.Bytes(), types/validator.go:
  * 154-170), as the light client checks it per header (light/verifier.go:266).
  * Set s holds validators [set_off[s], set_off[s+1]) in set order; validator
- * i: pk + 32*i, key_kind[i] (TMV_KIND_ED25519 / TMV_KIND_SR25519; secp256k1
- * keys are not supported), power[i].  hash_out: n_sets x 32 bytes (an empty
+ * i: pk + 32*i, key_kind[i] (TMV_KIND_ED25519 / TMV_KIND_SR25519; sets that
+ * hold 33-byte secp256k1 keys are hashed by the host layer), power[i].  hash_out: n_sets x 32 bytes (an empty
  * set hashes to SHA-256(""), as the reference).  set_off[0] must be 0.
  * Synchronous; 0 or < 0 on error. */
 int tmv_validator_set_hashes(tmv_ctx *ctx, const uint8_t *pk, const uint8_t *key_kind, const int64_t *power,
@@ -194,7 +214,7 @@ int tmv_verify_mixed_batch_ex(tmv_ctx *ctx, uint32_t flags, const uint8_t *kind,
 /* Live kernel timing (profiling aid; bench.py's roofline object).  enable != 0:
  * every later launch of the timed kernels -- "k_msm_accum" (batch-equation
  * bucket sums), "k_msm_wpart" (window running sums), "k_prep_fused" (decode +
- * challenge) -- is bracketed by HIP timing events on the stream it runs on
+ * challenge), "k_secp_prep" and "k_secp_verify" (secp256k1) -- is bracketed by HIP timing events on the stream it runs on
  * (process-wide, two event records per launch); 0 turns it off.
  * tmv_kernel_timing_read waits for the recorded launches of `kernel`, returns
  * their summed duration and count, and forgets them.  No reference

@@ -36,6 +36,7 @@ TMV_BATCHOPT_STATS = 1
 TMV_BATCHOPT_SUBCHECK_ON = 2
 TMV_BATCHOPT_SUBCHECK_OFF = 4
 TMV_KIND_MIXED = 2
+TMV_KIND_SECP256K1 = 3  # include/tmhost.h: 33-byte compressed keys, verified signature by signature
 TMV_VOTE_WITH_BLOCK = 0x80000000
 
 # tmv_vote (include/tmverify.h), 16 bytes
@@ -45,6 +46,7 @@ VOTE_DTYPE = np.dtype([("ts_seconds", "<i8"), ("ts_nanos", "<i4"), ("tmpl", "<u4
 EXPORTS = [
     "tmv_open", "tmv_open_logical", "tmv_close", "tmv_num_devices", "tmv_last_error", "tmv_version",
     "tmv_ed25519_verify_batch", "tmv_ed25519_verify", "tmv_sr25519_verify_batch",
+    "tmv_secp256k1_verify_batch", "tmv_secp256k1_verify",
     "tmv_verify_mixed_batch", "tmv_ed25519_verify_batch_device", "tmv_verify_mixed_batch_device",
     "tmv_verify_batch_ex", "tmv_key_cache_stats", "tmv_set_batch_options", "tmv_batch_stats",
     "tmv_subgroup_stats", "tmv_validator_set_hashes",
@@ -133,6 +135,8 @@ def lib() -> ctypes.CDLL:
         L.tmv_version.restype = ctypes.c_char_p
         L.tmv_ed25519_verify_batch.argtypes = [vp, u8p, u8p, u8p, u32p, ctypes.c_uint32, u8p]
         L.tmv_ed25519_verify.argtypes = [vp, u8p, u8p, ctypes.c_size_t, u8p, ctypes.c_size_t]
+        L.tmv_secp256k1_verify_batch.argtypes = [vp, u8p, u8p, u8p, u32p, ctypes.c_uint32, u8p]
+        L.tmv_secp256k1_verify.argtypes = [vp, u8p, ctypes.c_size_t, u8p, ctypes.c_size_t, u8p, ctypes.c_size_t]
         L.tmv_sr25519_verify_batch.argtypes = [vp, u8p, u8p, u8p, u32p, ctypes.c_uint32, i8p]
         L.tmv_verify_mixed_batch.argtypes = [vp, u8p, u8p, u8p, u8p, u32p, ctypes.c_uint32, i8p]
         L.tmv_verify_batch_ex.argtypes = [vp, ctypes.c_uint8, ctypes.c_uint32, u8p, u8p, u8p, u32p, ctypes.c_uint32,
@@ -248,6 +252,26 @@ class Context:
         s = np.frombuffer(sig + b"\0", np.uint8).copy()
         rc = self._check(self._lib.tmv_ed25519_verify(self._h, _p(a), _p(m), len(msg), _p(s), len(sig)),
                          "tmv_ed25519_verify")
+        return rc == 1
+
+    def secp256k1_verify_batch(self, pk: np.ndarray, sig: np.ndarray, msg: np.ndarray, off: np.ndarray):
+        """ECDSA over secp256k1, one verdict per entry; pk: n x 33 compressed keys, sig: n x 64 (r || s)."""
+        n = len(off) - 1
+        out = np.zeros(max(n, 1), np.uint8)
+        msg = msg if len(msg) else np.zeros(1, np.uint8)
+        pk = pk if len(pk) else np.zeros(1, np.uint8)
+        sig = sig if len(sig) else np.zeros(1, np.uint8)
+        rc = self._check(self._lib.tmv_secp256k1_verify_batch(self._h, _p(pk), _p(sig), _p(msg),
+                                                              _p(off, ctypes.c_uint32), n, _p(out)),
+                         "tmv_secp256k1_verify_batch")
+        return rc == TMV_ALL_VALID, out[:n]
+
+    def secp256k1_verify(self, pk: bytes, msg: bytes, sig: bytes) -> bool:
+        a = np.frombuffer(pk + b"\0", np.uint8).copy()
+        m = np.frombuffer(msg + b"\0", np.uint8).copy()
+        s = np.frombuffer(sig + b"\0", np.uint8).copy()
+        rc = self._check(self._lib.tmv_secp256k1_verify(self._h, _p(a), len(pk), _p(m), len(msg), _p(s), len(sig)),
+                         "tmv_secp256k1_verify")
         return rc == 1
 
     def sr25519_verify_batch(self, pk, sig, msg, off):

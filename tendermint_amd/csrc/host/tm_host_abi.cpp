@@ -24,6 +24,15 @@
 #include "tm_host_internal.h"
 #include "tm_light.h"
 #include "tm_types.h"
+#include "../secp256k1.h"
+
+// The engine's secp256k1 entry is a weak reference: libtmgpu.so defines it
+// (tmverify_runtime.cpp) and always uses it; a build of this file without the
+// engine (the CPU test double) loads all the same and verifies with the host
+// build of secp256k1.h -- the same code, the same verdicts.
+extern "C" int tmv_secp256k1_verify_batch(tmv_ctx *ctx, const uint8_t *pk, const uint8_t *sig, const uint8_t *msg,
+                                          const uint32_t *msg_off, uint32_t n, uint8_t *valid_out)
+    __attribute__((weak));
 
 namespace tmh_internal {
 
@@ -214,7 +223,7 @@ namespace tmh_internal {
 
 tmh::KeyType to_kind(uint8_t k) {
   return k == TMV_KIND_ED25519 ? tmh::KeyType::Ed25519 : k == TMV_KIND_SR25519 ? tmh::KeyType::Sr25519
-                                                                             : tmh::KeyType::Other;
+       : k == TMV_KIND_SECP256K1 ? tmh::KeyType::Secp256k1 : tmh::KeyType::Other;
 }
 
 tmh::Bytes bytes_of(const uint8_t *p, size_t n) { return p && n ? tmh::Bytes(p, p + n) : tmh::Bytes(); }
@@ -238,7 +247,7 @@ extern "C" {
 tmv_batch *tmv_batch_new(tmv_ctx *ctx, uint8_t key_kind) {
   if (!ctx) return nullptr;
   const tmh::KeyType k = to_kind(key_kind);
-  if (k == tmh::KeyType::Other) return nullptr;  // crypto/batch/batch.go:21
+  if (k != tmh::KeyType::Ed25519 && k != tmh::KeyType::Sr25519) return nullptr;  // crypto/batch/batch.go:13-21
   auto b = new tmv_batch;
   b->impl = std::make_unique<GpuBatch>(ctx, k);
   return b;
@@ -394,7 +403,8 @@ struct GpuBackend {
                                 vt.chain_len};
     }
     // verifier kind of every entry (2: not verified -- VerifySignature is
-    // false for a wrong key or signature size), classified in parallel
+    // false for a wrong key or signature size; 3: secp256k1, verified after
+    // the two batch kinds below), classified in parallel
     // chunks, then each kind's index list is filled chunk by chunk
     constexpr size_t kChunk = 4096;
     const size_t nch = (es.size() + kChunk - 1) / kChunk;
@@ -406,6 +416,7 @@ struct GpuBackend {
         const tmh::SigEntry &e = es[i].entry();
         uint8_t k = e.kind == tmh::KeyType::Ed25519 ? 0 : (e.kind == tmh::KeyType::Sr25519 ? 1 : 2);
         if (e.pk.size() != 32 || e.sig_len != 64) k = 2;
+        if (e.kind == tmh::KeyType::Secp256k1 && e.pk.size() == 33 && e.sig_len == 64) k = 3;
         pb.cls[i] = k;
         k0 += k == 0;
         k1 += k == 1;
@@ -477,6 +488,46 @@ struct GpuBackend {
       });
       tm.mark("b:scatter");
     }
+    VerifySecp256k1(es, tmpls, ent_tmpl, pb, st);
+  }
+
+  // The secp256k1 entries (class 3), each by PubKey.VerifySignature
+  // (crypto/secp256k1/secp256k1.go:206-226; types/validation.go:310-316 calls
+  // it per signature): messages encoded on the host from the commits'
+  // templates, one engine call, statuses scattered back.
+  void VerifySecp256k1(const std::vector<VoteRef> &es, const std::vector<tmh::VoteTemplate> &tmpls,
+                       const std::vector<uint32_t> &ent_tmpl, PackBuffers &pb, std::vector<int8_t> &st) {
+    std::vector<uint32_t> idx;
+    for (size_t i = 0; i < es.size(); i++)
+      if (pb.cls[i] == 3) idx.push_back((uint32_t)i);
+    const size_t m = idx.size();
+    if (m == 0) return;
+    std::vector<uint8_t> pk(33 * m), valid(m, 0);
+    pb.sig.resize(64 * m);
+    pb.off.assign(1, 0);
+    pb.msg.clear();
+    for (size_t t = 0; t < m; t++) {
+      const VoteRef &r = es[idx[t]];
+      const tmh::SigEntry &e = r.entry();
+      const tmh::CommitSig &cs = r.pl->commit->signatures[(size_t)r.pl->sig_idx[r.e]];
+      std::memcpy(&pk[33 * t], e.pk.data(), 33);
+      std::memcpy(&pb.sig[64 * t], e.sig, 64);
+      tmh::AppendVoteFromTemplate(pb.msg, tmpls[ent_tmpl[idx[t]]], cs.block_id_flag == tmh::BlockIDFlagCommit,
+                                  cs.timestamp);
+      pb.off.push_back((uint32_t)pb.msg.size());
+    }
+    if (pb.msg.empty()) pb.msg.push_back(0);
+    if (tmv_secp256k1_verify_batch) {  // the device entry (libtmgpu.so: always)
+      const int rc = tmv_secp256k1_verify_batch(ctx, pk.data(), pb.sig.data(), pb.msg.data(), pb.off.data(),
+                                                (uint32_t)m, valid.data());
+      if (rc < 0) { infra = rc; return; }
+    } else {  // no engine linked (the CPU test double): the same header's host build
+      parallel_for(m, 8, [&](size_t t) {
+        valid[t] = tmv::secp::secp256k1_verify_msg(&pk[33 * t], 33, pb.msg.data() + pb.off[t],
+                                                   pb.off[t + 1] - pb.off[t], &pb.sig[64 * t], 64) ? 1 : 0;
+      });
+    }
+    for (size_t t = 0; t < m; t++) st[idx[t]] = (int8_t)valid[t];
   }
 };
 

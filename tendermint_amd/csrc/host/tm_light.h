@@ -288,13 +288,14 @@ inline Bytes HeaderHashHost(const Header &h) {
 
 // ValidatorSet.Hash on the host (types/validator_set.go:344-350 over
 // SimpleValidator bytes, types/validator.go:154-170).  PublicKey oneof
-// (proto/tendermint/crypto/keys.proto): ed25519 = 1, secp256k1 = 2 (the only
-// other key type of the reference, KeyType::Other here), sr25519 = 3.
+// (proto/tendermint/crypto/keys.proto): ed25519 = 1, secp256k1 = 2 (also
+// written for KeyType::Other, as before the type had a name here), sr25519 = 3.
 inline Bytes ValidatorSetHashHost(const ValidatorSet &vs) {
   Bytes blob;
   std::vector<uint32_t> off{0};
   for (const Validator &v : vs.validators) {
-    const uint8_t field = v.pub_key.type == KeyType::Sr25519 ? 0x1a : v.pub_key.type == KeyType::Other ? 0x12 : 0x0a;
+    const bool secp = v.pub_key.type == KeyType::Secp256k1 || v.pub_key.type == KeyType::Other;
+    const uint8_t field = v.pub_key.type == KeyType::Sr25519 ? 0x1a : secp ? 0x12 : 0x0a;
     const size_t kl = v.pub_key.bytes.size();
     uint8_t tmp[16];
     blob.push_back(0x0a);

@@ -94,7 +94,7 @@ int valset_hashes(tmv_ctx *ctx, const std::vector<const tmh::ValidatorSet *> &vs
     if (!vs[i]) continue;
     bool ok = true;
     for (const tmh::Validator &v : vs[i]->validators)
-      ok = ok && v.pub_key.type != tmh::KeyType::Other && v.pub_key.bytes.size() == 32;
+      ok = ok && tmh::SupportsBatchVerifier(v.pub_key) && v.pub_key.bytes.size() == 32;  // ed25519 / sr25519
     (ok ? dev : host).push_back(i);
   }
   if (dev.size() < device_hash_min()) {

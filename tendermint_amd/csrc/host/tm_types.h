@@ -115,7 +115,7 @@ inline std::string CanonicalTime(const Timestamp &t) {
 }
 
 // ---------------------------------------------------------------- keys
-enum class KeyType : uint8_t { Ed25519 = 0, Sr25519 = 1, Other = 255 };
+enum class KeyType : uint8_t { Ed25519 = 0, Sr25519 = 1, Secp256k1 = 3, Other = 255 };
 
 // A public key: its type and a view of its bytes (the caller's tmv_validator
 // / tmv_batch_add arguments, which outlive the call that reads them).
@@ -123,11 +123,13 @@ struct PubKey {
   KeyType type = KeyType::Ed25519;
   ByteView bytes;
   std::string Type() const {
-    return type == KeyType::Ed25519 ? "ed25519" : type == KeyType::Sr25519 ? "sr25519" : "other";
+    return type == KeyType::Ed25519 ? "ed25519" : type == KeyType::Sr25519 ? "sr25519"
+         : type == KeyType::Secp256k1 ? "secp256k1" : "other";
   }
   std::string String() const {  // crypto/ed25519/ed25519.go:182, crypto/sr25519/pubkey.go:68
     if (type == KeyType::Ed25519) return "PubKeyEd25519{" + HexUpper(bytes) + "}";
     if (type == KeyType::Sr25519) return "PubKeySr25519{" + HexUpper(bytes) + "}";
+    if (type == KeyType::Secp256k1) return "PubKeySecp256k1{" + HexUpper(bytes) + "}";  // secp256k1.go:170
     return "PubKey{" + HexUpper(bytes) + "}";
   }
 };

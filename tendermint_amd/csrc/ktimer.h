@@ -10,7 +10,7 @@
 namespace tmv {
 namespace ktimer {
 
-enum Kernel : int { kAccum = 0, kWpart = 1, kPrep = 2, kCount = 3 };
+enum Kernel : int { kAccum = 0, kWpart = 1, kPrep = 2, kSecpPrep = 3, kSecpVerify = 4, kCount = 5 };
 
 void set(bool on);
 bool on();

@@ -41,6 +41,8 @@
 #include "verify_kernels.h"
 #include "votes.h"
 #include "valset.h"
+#include "secp256k1.h"
+#include "secp256k1_launch.h"
 
 namespace {
 
@@ -246,6 +248,8 @@ struct Device {
   uint64_t kepoch = 0, khits = 0, kmisses = 0;
   DeviceBuf d_kbuild, h_kbuild;
   DeviceBuf d_valset, h_valset;  // tmv_validator_set_hashes staging
+  uint32_t *d_secp_gtab = nullptr;             // secp256k1: j G, j = 1..15, affine (secp256k1.h)
+  DeviceBuf d_secp_in, h_secp_in, d_secp_work; // tmv_secp256k1_verify_batch staging and workspace
   // host-buffer launches: key slots of the shard and the per-chunk key
   // histograms of the key-merged form's counting sort
   std::vector<uint32_t> slots, key_count;
@@ -776,6 +780,14 @@ static int init_device(Device &d) {
   if (e != hipSuccess) { set_error("hipMalloc(btable)", e); return TMV_ERR_NOMEM; }
   e = hipMemcpy(d.d_btable, table.data(), bytes, hipMemcpyHostToDevice);
   if (e != hipSuccess) { set_error("hipMemcpy(btable)", e); return TMV_ERR_NO_DEVICE; }
+  {  // secp256k1 G table, from the same header the kernels use
+    std::vector<uint32_t> gt(tmv::secp::kGTableWords);
+    tmv::secp::build_g_table(gt.data());
+    e = hipMalloc(&d.d_secp_gtab, gt.size() * sizeof(uint32_t));
+    if (e != hipSuccess) { set_error("hipMalloc(secp gtab)", e); return TMV_ERR_NOMEM; }
+    e = hipMemcpy(d.d_secp_gtab, gt.data(), gt.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { set_error("hipMemcpy(secp gtab)", e); return TMV_ERR_NO_DEVICE; }
+  }
   // quad B tables: entry m = (m+1)B, then entry kBaseQuadEntries + m =
   // (m+1)[2^128]B (the half-size scalars' top digits), m < kBaseQuadEntries,
   // as (ymx, ypx, xy2d, 1)
@@ -1399,6 +1411,8 @@ int tmv_kernel_timing_read(tmv_ctx *ctx, const char *kernel, double *total_ms, u
   if (!strcmp(kernel, "k_msm_accum")) k = tmv::ktimer::kAccum;
   else if (!strcmp(kernel, "k_msm_wpart")) k = tmv::ktimer::kWpart;
   else if (!strcmp(kernel, "k_prep_fused")) k = tmv::ktimer::kPrep;
+  else if (!strcmp(kernel, "k_secp_prep")) k = tmv::ktimer::kSecpPrep;
+  else if (!strcmp(kernel, "k_secp_verify")) k = tmv::ktimer::kSecpVerify;
   else { set_error("unknown timed kernel"); return TMV_ERR_ARG; }
   *total_ms = 0;
   *launches = 0;
@@ -1549,6 +1563,10 @@ void tmv_close(tmv_ctx *ctx) {
     if (d->work_done) (void)hipEventDestroy(d->work_done);
     if (d->kbuild_copied) (void)hipEventDestroy(d->kbuild_copied);
     if (d->d_btable) (void)hipFree(d->d_btable);
+    if (d->d_secp_gtab) (void)hipFree(d->d_secp_gtab);
+    d->d_secp_in.release();
+    d->h_secp_in.release();
+    d->d_secp_work.release();
     for (int l = 0; l < kLanes; l++)
       if (d->lane[l].stream) (void)hipStreamDestroy(d->lane[l].stream);
     if (d->stream) (void)hipStreamDestroy(d->stream);
@@ -2524,9 +2542,87 @@ int tmv_merkle_roots(tmv_ctx *ctx, const uint8_t *data, const uint32_t *leaf_off
   return 0;
 }
 
+// secp256k1 ECDSA batch (crypto/secp256k1/secp256k1.go:206-226 per entry).
+// Synchronous, host buffers, device 0; staged like tmv_merkle_roots: one H2D
+// copy (keys padded to 48 bytes), the launches (in chunks that bound the Q
+// table workspace), one D2H copy.
+int tmv_secp256k1_verify_batch(tmv_ctx *ctx, const uint8_t *pk, const uint8_t *sig, const uint8_t *msg,
+                               const uint32_t *msg_off, uint32_t n, uint8_t *valid_out) {
+  if (!ctx || ctx->devs.empty()) { set_error("null context"); return TMV_ERR_ARG; }
+  if (n == 0) return TMV_NOT_ALL;
+  if (!pk || !sig || !msg_off || !valid_out) { set_error("tmv_secp256k1_verify_batch: null pointer"); return TMV_ERR_ARG; }
+  if (n > (1u << 26)) { set_error("tmv_secp256k1_verify_batch: too many entries"); return TMV_ERR_ARG; }
+  if (msg_off[0] != 0) { set_error("tmv_secp256k1_verify_batch: msg_off[0] must be 0"); return TMV_ERR_ARG; }
+  for (uint32_t i = 0; i < n; i++)
+    if (msg_off[i + 1] < msg_off[i]) { set_error("tmv_secp256k1_verify_batch: msg_off decreasing"); return TMV_ERR_ARG; }
+  const uint32_t bytes = msg_off[n];
+  if (bytes > (1u << 30)) { set_error("tmv_secp256k1_verify_batch: messages too large"); return TMV_ERR_ARG; }
+  if (bytes && !msg) { set_error("tmv_secp256k1_verify_batch: null msg"); return TMV_ERR_ARG; }
+  ctx->count_call(n);
+  Device &d = *ctx->devs[0];
+  std::lock_guard<std::mutex> lk(d.mu);
+  if (d.faulted) return faulted_rc(d);
+  hipError_t e = hipSetDevice(d.id);
+  if (e != hipSuccess) { set_error("hipSetDevice", e); return TMV_ERR_NO_DEVICE; }
+  // staging: pk48 | sig | msg_off | msg, then (device only) the statuses
+  constexpr uint32_t kChunk = 262144;  // entries per launch pair: 2,176 bytes of workspace each
+  const size_t o_sig = 48ull * n, o_off = o_sig + 64ull * n, o_msg = o_off + align16(4ull * (n + 1));
+  const size_t in_bytes = o_msg + align16(bytes), o_out = in_bytes, dev_bytes = o_out + align16(n);
+  hipStream_t s = context_stream(d);
+  if (!s) { set_error("hipStreamCreate failed"); return TMV_ERR_NO_DEVICE; }
+  if ((e = wait_stream(d, s)) != hipSuccess) return wait_rc(e);  // staging may still feed an earlier call
+  if ((e = d.h_secp_in.ensure(in_bytes, true)) != hipSuccess) { set_error("hipHostMalloc", e); return TMV_ERR_NOMEM; }
+  if ((e = d.d_secp_in.ensure(dev_bytes, false)) != hipSuccess) { set_error("hipMalloc", e); return TMV_ERR_NOMEM; }
+  if ((e = d.d_secp_work.ensure(tmv::secp256k1_workspace_bytes(std::min(n, kChunk)), false)) != hipSuccess) {
+    set_error("hipMalloc(secp work)", e);
+    return TMV_ERR_NOMEM;
+  }
+  uint8_t *h = static_cast<uint8_t *>(d.h_secp_in.ptr);
+  for (uint32_t i = 0; i < n; i++) {
+    std::memcpy(h + 48ull * i, pk + 33ull * i, 33);
+    std::memset(h + 48ull * i + 33, 0, 15);
+  }
+  std::memcpy(h + o_sig, sig, 64ull * n);
+  std::memcpy(h + o_off, msg_off, 4ull * (n + 1));
+  if (bytes) std::memcpy(h + o_msg, msg, bytes);
+  uint8_t *g = static_cast<uint8_t *>(d.d_secp_in.ptr);
+  if ((e = hipMemcpyAsync(g, h, in_bytes, hipMemcpyHostToDevice, s)) != hipSuccess) {
+    set_error("hipMemcpyAsync(secp256k1)", e);
+    return TMV_ERR_LAUNCH;
+  }
+  for (uint32_t lo = 0; lo < n; lo += kChunk) {
+    const uint32_t m = std::min(kChunk, n - lo);
+    e = tmv::launch_secp256k1_verify(g + 48ull * lo, g + o_sig + 64ull * lo, g + o_msg,
+                                     reinterpret_cast<const uint32_t *>(g + o_off) + lo, m, d.d_secp_gtab,
+                                     static_cast<uint8_t *>(d.d_secp_work.ptr), g + o_out + lo, s);
+    if (e != hipSuccess) { set_error("secp256k1 launch", e); return TMV_ERR_LAUNCH; }
+  }
+  if ((e = hipMemcpyAsync(valid_out, g + o_out, n, hipMemcpyDeviceToHost, s)) != hipSuccess ||
+      (e = wait_stream(d, s)) != hipSuccess) {
+    if (e != hipErrorNotReady) set_error("secp256k1 readback", e);
+    return wait_rc(e);
+  }
+  bool all = true;
+  for (uint32_t i = 0; i < n; i++) all = all && valid_out[i] == 1;
+  return all ? TMV_ALL_VALID : TMV_NOT_ALL;
+}
+
 }  // extern "C"
 
 extern "C" {
+
+// Single secp256k1 verification (secp256k1.go:206-226: false for any other
+// key or signature size, without touching the device).
+int tmv_secp256k1_verify(tmv_ctx *ctx, const uint8_t *pk, size_t pk_len, const uint8_t *msg, size_t msg_len,
+                         const uint8_t *sig, size_t sig_len) {
+  if (pk_len != 33 || sig_len != 64) return 0;
+  if (msg_len > (1u << 30)) { set_error("message too long"); return TMV_ERR_ARG; }
+  uint32_t off[2] = {0, (uint32_t)msg_len};
+  uint8_t v = 0;
+  static const uint8_t empty = 0;
+  int rc = tmv_secp256k1_verify_batch(ctx, pk, sig, msg ? msg : &empty, off, 1, &v);
+  return rc < 0 ? rc : (int)v;
+}
 
 int tmv_ed25519_verify(tmv_ctx *ctx, const uint8_t *pk, const uint8_t *msg, size_t msg_len, const uint8_t *sig,
                        size_t sig_len) {

@@ -17,7 +17,7 @@ from dataclasses import dataclass, field
 from typing import List, Optional, Tuple
 
 from . import _native
-from ._native import NativeError, TMV_KIND_ED25519, TMV_KIND_SR25519
+from ._native import NativeError, TMV_KIND_ED25519, TMV_KIND_SR25519, TMV_KIND_SECP256K1
 
 KIND_OTHER = 255
 BLOCK_ID_FLAG_ABSENT, BLOCK_ID_FLAG_COMMIT, BLOCK_ID_FLAG_NIL = 1, 2, 3

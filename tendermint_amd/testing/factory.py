@@ -309,7 +309,8 @@ def make_c1_commit(n_vals: int = 150, chain_id: str = "test_chain_id", height: i
 
 def _simple_validator_bytes(v) -> bytes:
     """Validator.Bytes() (types/validator.go:154-170): SimpleValidator protobuf."""
-    pub = bytes([(3 if v.key_kind == 1 else 1) << 3 | 2, 32]) + v.pub_key  # kind 1 = sr25519: oneof field 3
+    # PublicKey oneof: ed25519 = 1, secp256k1 = 2 (kind 3, 33-byte keys), sr25519 = 3 (kind 1)
+    pub = bytes([{1: 3, 3: 2}.get(v.key_kind, 1) << 3 | 2, len(v.pub_key)]) + v.pub_key
     out = bytes([0x0A, len(pub)]) + pub
     if v.voting_power:
         u, var = v.voting_power & ((1 << 64) - 1), bytearray()
