@@ -246,6 +246,80 @@ int tmv_light_verify_many(tmv_ctx *ctx, const tmv_light_job *jobs, uint32_t n_jo
 /* One job: returns its TMV_LIGHT_* class (text in err) or < 0. */
 int tmv_light_verify(tmv_ctx *ctx, const tmv_light_job *job, char *err, size_t err_cap);
 
+/* ---- block part sets and merkle proofs (types/part_set.go, crypto/merkle/proof.go) ---- */
+/* Above $TMV_DEVICE_MERKLE_MIN bytes of leaves per call (default 64 MiB: below
+ * it a 64 KiB part's serial SHA-256 chain on one lane outlasts 16 host
+ * threads) these calls hash on the device
+ * (tmv_merkle_proofs / tmv_merkle_verify_proofs, reached through weak
+ * references), below it, and in a build without the engine, on the host --
+ * the same verdicts and texts either way. */
+
+/* merkle.Proof (proof.go:26-31). */
+typedef struct {
+  int64_t total, index;
+  tmv_bytes leaf_hash;
+  const tmv_bytes *aunts;
+  uint32_t n_aunts;
+} tmv_proof;
+
+/* NewPartSetFromData(data, partSize).Header() (types/part_set.go:172-222) of n
+ * serialised blocks: what blocksync's replay loop computes per block
+ * (internal/blocksync/reactor.go:563-582, first.MakePartSet) for the BlockID
+ * that VerifyCommitLight checks.  total_out[b] = ceil(len / part_size) in the
+ * reference's uint32 arithmetic (a partial last part is allowed; empty data:
+ * 0 parts and SHA-256("")); hash_out: n x 32.  part_size == 0 is TMV_ERR_ARG.
+ * Windows above the engine's 1 GiB take several engine calls.  0 or < 0. */
+int tmv_part_set_headers(tmv_ctx *ctx, const tmv_bytes *blocks, uint32_t n, uint32_t part_size, uint32_t *total_out,
+                         uint8_t *hash_out);
+/* The same with each part's merkle.Proof (Part.Proof, part_set.go:187-191).
+ * The parts of all blocks are numbered one after the other (block b's first
+ * part is the sum of the totals before it): part p has Proof.Total =
+ * total_out[b], Proof.Index = its index in the block, LeafHash =
+ * leaf_hash_out + 32*p and the aunts aunts_out[32*aunt_off_out[p] ..
+ * 32*aunt_off_out[p+1]), leaf sibling first.  leaf_hash_out holds parts x 32
+ * bytes, aunt_off_out parts + 1 entries, aunts_out aunts_cap hashes
+ * (TMV_ERR_ARG when that is too few; parts * 32 always suffices). */
+int tmv_part_set_proofs(tmv_ctx *ctx, const tmv_bytes *blocks, uint32_t n, uint32_t part_size, uint32_t *total_out,
+                        uint8_t *hash_out, uint8_t *leaf_hash_out, uint32_t *aunt_off_out, uint8_t *aunts_out,
+                        uint64_t aunts_cap);
+
+/* A received part with the header of the set it is offered to. */
+typedef struct {
+  uint32_t index;     /* Part.Index */
+  tmv_bytes bytes;    /* Part.Bytes */
+  tmv_proof proof;    /* Part.Proof */
+  uint32_t set_total; /* PartSetHeader.Total */
+  tmv_bytes set_hash; /* PartSetHeader.Hash */
+} tmv_part_in;
+
+#define TMV_PART_OK 0
+#define TMV_PART_ERR_UNEXPECTED_INDEX 1 /* types.ErrPartSetUnexpectedIndex: "error part set unexpected index" */
+#define TMV_PART_ERR_INVALID_PROOF 2    /* types.ErrPartSetInvalidProof: "error part set invalid proof" */
+
+/* PartSet.AddPart's checks (types/part_set.go:272-300) for n parts:
+ * part.Index >= total, then part.Proof.Verify(ps.Hash(), part.Bytes).  As the
+ * reference, it compares neither proof.Index with part.Index nor proof.Total
+ * with the header's total.  results[i] = TMV_PART_*, the error's text at
+ * errs + i*err_stride (errs may be NULL).  Returns the number of failed parts
+ * or < 0. */
+int tmv_parts_verify(tmv_ctx *ctx, const tmv_part_in *parts, uint32_t n, int32_t *results, char *errs,
+                     size_t err_stride);
+
+/* One proof with the leaf and root it is checked against. */
+typedef struct {
+  tmv_proof proof;
+  tmv_bytes leaf;
+  tmv_bytes root;
+} tmv_proof_in;
+
+/* Proof.ValidateBasic (proof.go:98-117) then Proof.Verify (proof.go:52-68) of
+ * n proofs: results[i] = 0 ok / 1 error with the reference's text at
+ * errs + i*err_stride ("negative Total", ..., "invalid root hash: wanted %X
+ * got %X", a nil computed root printing as nothing).  Returns the number of
+ * failed proofs or < 0. */
+int tmv_proofs_verify(tmv_ctx *ctx, const tmv_proof_in *items, uint32_t n, int32_t *results, char *errs,
+                      size_t err_stride);
+
 #ifdef __cplusplus
 }
 #endif

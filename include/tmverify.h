@@ -200,6 +200,65 @@ int tmv_validator_set_hashes(tmv_ctx *ctx, const uint8_t *pk, const uint8_t *key
  * < 0 on error. */
 int tmv_merkle_roots(tmv_ctx *ctx, const uint8_t *data, const uint32_t *leaf_off, uint32_t n_leaves,
                      const uint32_t *tree_off, uint32_t n_trees, uint8_t *hash_out);
+
+/* Merkle inclusion proofs (crypto/merkle/proof.go).  Blocksync's replay loop
+ * builds every block's part set (internal/blocksync/reactor.go:563-582:
+ * first.MakePartSet -> NewPartSetFromData, types/part_set.go:172-200 ->
+ * merkle.ProofsFromByteSlices over the 64 KiB parts) for the BlockID that
+ * VerifyCommitLight checks; PartSet.AddPart verifies each received part's
+ * proof (types/part_set.go:272-300); Txs.Hash / Txs.Proof run the same tree
+ * over SHA-256(tx) (types/tx.go:30-75).
+ * flags of both calls:
+ *   TMV_MERKLE_PREHASH          the leaf is SHA-256(0x00 || SHA-256(item)):
+ *                               the items are hashed first, as Txs.Hash does
+ *   TMV_MERKLE_LEAF_HASH_GIVEN  (verify) no leaves are supplied; leaf_hash is
+ *                               taken as Proof.Verify's leafHash(leaf)
+ *   TMV_MERKLE_LONG_LEAVES / TMV_MERKLE_SHORT_LEAVES, TMV_MERKLE_LPW(8|16|32|64)
+ *                               tuning aids: force the long-leaf kernel / the
+ *                               byte-wise kernel of tmv_merkle_roots, and the
+ *                               long-leaf kernel's leaves per wave.  Default:
+ *                               the long-leaf kernel when the leaves average
+ *                               >= $TMV_MERKLE_LONG_MIN bytes (512) or with
+ *                               TMV_MERKLE_PREHASH, leaves per wave from the
+ *                               leaf count.  Results do not depend on them. */
+#define TMV_MERKLE_PREHASH 1u
+#define TMV_MERKLE_LEAF_HASH_GIVEN 2u
+#define TMV_MERKLE_LONG_LEAVES 4u
+#define TMV_MERKLE_SHORT_LEAVES 8u
+#define TMV_MERKLE_LPW(l) ((uint32_t)(l) << 8)
+/* A proof's aunt count depends on (index, total) alone: aunt_off_out[i] is the
+ * number of aunts of all leaves before leaf i of n_trees trees laid out as for
+ * tmv_merkle_roots (tree_off[n_trees] + 1 entries; no device work). */
+int tmv_merkle_aunt_offsets(const uint32_t *tree_off, uint32_t n_trees, uint32_t *aunt_off_out);
+/* merkle.ProofsFromByteSlices (proof.go:33-48) of n_trees trees in one call;
+ * data, leaf_off, tree_off as for tmv_merkle_roots.  root_out: n_trees x 32
+ * (an empty tree: SHA-256("")); leaf_hash_out: n_leaves x 32 (Proof.LeafHash);
+ * the aunts of leaf i, leaf sibling first (FlattenAunts, proof.go:197-215),
+ * are aunts_out[32*aunt_off[i] .. 32*aunt_off[i+1]) with aunt_off from
+ * tmv_merkle_aunt_offsets (anything else is TMV_ERR_ARG).  aunts_out == NULL:
+ * roots and leaf hashes only (MakePartSet().Header()).  Proof i has Total =
+ * its tree's leaf count and Index = i - tree_off[t].  Synchronous, device 0;
+ * limits and errors as tmv_merkle_roots; 0 or < 0. */
+int tmv_merkle_proofs(tmv_ctx *ctx, uint32_t flags, const uint8_t *data, const uint32_t *leaf_off, uint32_t n_leaves,
+                      const uint32_t *tree_off, uint32_t n_trees, uint8_t *root_out, uint8_t *leaf_hash_out,
+                      const uint32_t *aunt_off, uint8_t *aunts_out);
+/* Proof.Verify (proof.go:52-68) of n proofs.  Proof i: total[i], index[i],
+ * leaf_hash + 32*i, aunts[32*aunt_off[i] .. 32*aunt_off[i+1]) (any count),
+ * checked against root + 32*i and the leaf data[leaf_off[i], leaf_off[i+1])
+ * (data / leaf_off unused with TMV_MERKLE_LEAF_HASH_GIVEN).  status_out[i], in
+ * the reference's order of tests: 0 ok, 1 total < 0, 2 index < 0, 3 the leaf's
+ * hash differs from leaf_hash, 4 the root computed from leaf_hash and the
+ * aunts (computeHashFromAunts, proof.go:151-181) differs from root or is nil
+ * (index >= total, total == 0, or an aunt count that does not fit the path).
+ * Optional outputs (NULL to skip): leaf_hash_calc n x 32 (the hashed leaf;
+ * leaf_hash itself when given), root_calc n x 32 (zeros when nil), root_nil n.
+ * Returns 0 (every status 0), 1 (some not) or < 0; n <= 2^26, leaves <= 2^30
+ * bytes, <= 2^28 aunts. */
+int tmv_merkle_verify_proofs(tmv_ctx *ctx, uint32_t flags, uint32_t n, const int64_t *total, const int64_t *index,
+                             const uint8_t *leaf_hash, const uint8_t *aunts, const uint32_t *aunt_off,
+                             const uint8_t *root, const uint8_t *data, const uint32_t *leaf_off, int8_t *status_out,
+                             uint8_t *leaf_hash_calc, uint8_t *root_calc, uint8_t *root_nil);
+
 /* Sub-groups of failing groups checked / failed (k_msm_subcheck: a failing
  * group's sub-groups of 8 entries are re-checked with the same equation
  * before entry-by-entry verification; TMV_BATCHOPT_STATS; 0 with
@@ -214,7 +273,9 @@ int tmv_verify_mixed_batch_ex(tmv_ctx *ctx, uint32_t flags, const uint8_t *kind,
 /* Live kernel timing (profiling aid; bench.py's roofline object).  enable != 0:
  * every later launch of the timed kernels -- "k_msm_accum" (batch-equation
  * bucket sums), "k_msm_wpart" (window running sums), "k_prep_fused" (decode +
- * challenge), "k_secp_prep" and "k_secp_verify" (secp256k1) -- is bracketed by HIP timing events on the stream it runs on
+ * challenge), "k_secp_prep" and "k_secp_verify" (secp256k1), "k_merkle_leaves_long",
+ * "k_merkle_leaves", "k_merkle_tree_levels", "k_merkle_aunts" and "k_merkle_verify_proofs" (the launches
+ * of tmv_merkle_proofs / tmv_merkle_verify_proofs) -- is bracketed by HIP timing events on the stream it runs on
  * (process-wide, two event records per launch); 0 turns it off.
  * tmv_kernel_timing_read waits for the recorded launches of `kernel`, returns
  * their summed duration and count, and forgets them.  No reference

@@ -35,6 +35,10 @@ TMV_FLAG_PER_ENTRY = 4
 TMV_BATCHOPT_STATS = 1
 TMV_BATCHOPT_SUBCHECK_ON = 2
 TMV_BATCHOPT_SUBCHECK_OFF = 4
+TMV_MERKLE_PREHASH = 1
+TMV_MERKLE_LEAF_HASH_GIVEN = 2
+TMV_MERKLE_LONG_LEAVES = 4
+TMV_MERKLE_SHORT_LEAVES = 8
 TMV_KIND_MIXED = 2
 TMV_KIND_SECP256K1 = 3  # include/tmhost.h: 33-byte compressed keys, verified signature by signature
 TMV_VOTE_WITH_BLOCK = 0x80000000
@@ -52,11 +56,13 @@ EXPORTS = [
     "tmv_subgroup_stats", "tmv_validator_set_hashes",
     "tmv_verify_mixed_batch_ex", "tmv_verify_batch_device_ex", "tmv_verify_batches_device",
     "tmv_verify_votes", "tmv_vote_sign_bytes_device", "tmv_merkle_roots",
+    "tmv_merkle_aunt_offsets", "tmv_merkle_proofs", "tmv_merkle_verify_proofs",
     "tmv_kernel_timing", "tmv_kernel_timing_read", "tmv_metrics_read", "tmv_metrics_reset",
     # include/tmhost.h
     "tmv_batch_new", "tmv_batch_add", "tmv_batch_len", "tmv_batch_verify", "tmv_batch_free",
     "tmv_vote_sign_bytes", "tmv_vote_template_encode", "tmv_verify_commit", "tmv_verify_commits",
     "tmv_header_hashes", "tmv_light_verify_many", "tmv_light_verify", "tmv_verify_vote_batch",
+    "tmv_part_set_headers", "tmv_part_set_proofs", "tmv_parts_verify", "tmv_proofs_verify",
 ]
 
 
@@ -152,6 +158,13 @@ def lib() -> ctypes.CDLL:
         L.tmv_validator_set_hashes.argtypes = [vp, u8p, u8p, ctypes.POINTER(ctypes.c_int64), u32p,
                                                ctypes.c_uint32, u8p]
         L.tmv_verify_mixed_batch_ex.argtypes = [vp, ctypes.c_uint32, u8p, u8p, u8p, u8p, u32p, ctypes.c_uint32, i8p]
+        L.tmv_merkle_roots.argtypes = [vp, u8p, u32p, ctypes.c_uint32, u32p, ctypes.c_uint32, u8p]
+        L.tmv_merkle_aunt_offsets.argtypes = [u32p, ctypes.c_uint32, u32p]
+        L.tmv_merkle_proofs.argtypes = [vp, ctypes.c_uint32, u8p, u32p, ctypes.c_uint32, u32p, ctypes.c_uint32, u8p,
+                                        u8p, u32p, u8p]
+        i64p = ctypes.POINTER(ctypes.c_int64)
+        L.tmv_merkle_verify_proofs.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, i64p, i64p, u8p, u8p, u32p, u8p,
+                                               u8p, u32p, i8p, u8p, u8p, u8p]
         L.tmv_verify_batch_device_ex.argtypes = [vp, ctypes.c_int, ctypes.c_uint8, ctypes.c_uint32, vp, vp, vp, vp,
                                                  vp, ctypes.c_uint32, vp, vp]
         L.tmv_verify_batches_device.argtypes = [vp, ctypes.c_int, ctypes.c_uint8, ctypes.c_uint32,
@@ -167,6 +180,21 @@ def lib() -> ctypes.CDLL:
         L.tmv_metrics_reset.argtypes = [vp]
         _lib = L
         return L
+
+
+def merkle_lpw(leaves_per_wave: int) -> int:
+    """TMV_MERKLE_LPW(l): the flag bits that fix the long-leaf kernel's leaves per wave."""
+    return leaves_per_wave << 8
+
+
+def merkle_aunt_offsets(tree_off: np.ndarray) -> np.ndarray:
+    """tmv_merkle_aunt_offsets: prefix sums of every leaf's aunt count (no device work)."""
+    tree_off = np.ascontiguousarray(tree_off, np.uint32)
+    out = np.zeros(int(tree_off[-1]) + 1, np.uint32)
+    rc = lib().tmv_merkle_aunt_offsets(_p(tree_off, ctypes.c_uint32), len(tree_off) - 1, _p(out, ctypes.c_uint32))
+    if rc < 0:
+        raise NativeError(f"tmv_merkle_aunt_offsets failed ({rc}): {last_error()}")
+    return out
 
 
 def last_error() -> str:
@@ -393,6 +421,72 @@ class Context:
                                                        _p(set_off, ctypes.c_uint32), n_sets, _p(out)),
                     "tmv_validator_set_hashes")
         return out[:n_sets]
+
+    def merkle_roots(self, data, leaf_off: np.ndarray, tree_off: np.ndarray) -> np.ndarray:
+        """merkle.HashFromByteSlices of each tree (tmv_merkle_roots): (n_trees, 32) uint8.
+        data: uint8 array, or None for a null pointer."""
+        n_trees, n_leaves = len(tree_off) - 1, len(leaf_off) - 1
+        out = np.zeros((max(n_trees, 1), 32), np.uint8)
+        leaf_off = np.ascontiguousarray(leaf_off, np.uint32)
+        tree_off = np.ascontiguousarray(tree_off, np.uint32)
+        dp = None if data is None else _p(np.ascontiguousarray(data, np.uint8) if len(data) else np.zeros(1, np.uint8))
+        self._check(self._lib.tmv_merkle_roots(self._h, dp, _p(leaf_off, ctypes.c_uint32), n_leaves,
+                                               _p(tree_off, ctypes.c_uint32), n_trees, _p(out)), "tmv_merkle_roots")
+        return out[:n_trees]
+
+    def merkle_proofs(self, data, leaf_off: np.ndarray, tree_off: np.ndarray, flags: int = 0, aunts: bool = True):
+        """merkle.ProofsFromByteSlices of each tree (tmv_merkle_proofs):
+        (roots (n_trees, 32), leaf hashes (n_leaves, 32), aunt_off (n_leaves + 1)
+        or None, aunts (n_aunts, 32) or None).  Leaf i's aunts, leaf sibling
+        first, are aunts[aunt_off[i]:aunt_off[i+1]]; its proof has total = its
+        tree's leaf count and index = i - tree_off[t].  data: uint8 array, or
+        None for a null pointer."""
+        n_trees, n_leaves = len(tree_off) - 1, len(leaf_off) - 1
+        leaf_off = np.ascontiguousarray(leaf_off, np.uint32)
+        tree_off = np.ascontiguousarray(tree_off, np.uint32)
+        dp = None if data is None else _p(np.ascontiguousarray(data, np.uint8) if len(data) else np.zeros(1, np.uint8))
+        roots = np.zeros((max(n_trees, 1), 32), np.uint8)
+        leaves = np.zeros((max(n_leaves, 1), 32), np.uint8)
+        aoff = av = None
+        if aunts:
+            aoff = merkle_aunt_offsets(tree_off)
+            av = np.zeros((max(int(aoff[-1]), 1), 32), np.uint8)
+        self._check(self._lib.tmv_merkle_proofs(self._h, flags, dp, _p(leaf_off, ctypes.c_uint32), n_leaves,
+                                                _p(tree_off, ctypes.c_uint32), n_trees, _p(roots), _p(leaves),
+                                                _p(aoff, ctypes.c_uint32) if aunts else None,
+                                                _p(av) if aunts else None), "tmv_merkle_proofs")
+        return roots[:n_trees], leaves[:n_leaves], aoff, (av[:int(aoff[-1])] if aunts else None)
+
+    def merkle_verify_proofs(self, total, index, leaf_hash, aunts, aunt_off, root, data=None, leaf_off=None,
+                             flags: int = 0):
+        """Proof.Verify of n proofs (tmv_merkle_verify_proofs): (all ok,
+        status (n,) int8, computed leaf hashes (n, 32), computed roots (n, 32),
+        root-is-nil flags (n,)).  Without data / leaf_off the leaf hashes are
+        taken as given (TMV_MERKLE_LEAF_HASH_GIVEN)."""
+        n = len(total)
+        total = np.ascontiguousarray(total, np.int64) if n else np.zeros(1, np.int64)
+        index = np.ascontiguousarray(index, np.int64) if n else np.zeros(1, np.int64)
+        leaf_hash = np.ascontiguousarray(leaf_hash, np.uint8) if n else np.zeros(32, np.uint8)
+        root = np.ascontiguousarray(root, np.uint8) if n else np.zeros(32, np.uint8)
+        aunt_off = np.ascontiguousarray(aunt_off, np.uint32)
+        aunts = np.ascontiguousarray(aunts, np.uint8) if len(aunts) else np.zeros(32, np.uint8)
+        if leaf_off is None:
+            flags |= TMV_MERKLE_LEAF_HASH_GIVEN
+            dp = lp = None
+        else:
+            leaf_off = np.ascontiguousarray(leaf_off, np.uint32)
+            lp = _p(leaf_off, ctypes.c_uint32)
+            dp = None if data is None else _p(np.ascontiguousarray(data, np.uint8) if len(data)
+                                              else np.zeros(1, np.uint8))
+        status = np.zeros(max(n, 1), np.int8)
+        lcalc = np.zeros((max(n, 1), 32), np.uint8)
+        rcalc = np.zeros((max(n, 1), 32), np.uint8)
+        nil = np.zeros(max(n, 1), np.uint8)
+        rc = self._check(self._lib.tmv_merkle_verify_proofs(
+            self._h, flags, n, _p(total, ctypes.c_int64), _p(index, ctypes.c_int64), _p(leaf_hash), _p(aunts),
+            _p(aunt_off, ctypes.c_uint32), _p(root), dp, lp, _p(status, ctypes.c_int8), _p(lcalc), _p(rcalc),
+            _p(nil)), "tmv_merkle_verify_proofs")
+        return rc == 0, status[:n], lcalc[:n], rcalc[:n], nil[:n]
 
     def batch_stats(self):
         g, f = ctypes.c_uint64(), ctypes.c_uint64()

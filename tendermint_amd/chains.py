@@ -296,3 +296,53 @@ def blocksync_replay(ctx, chain_id: str, vals: H.ValidatorSet, blocks: List[Bloc
                 return applied, (height, err)
             applied += 1
     return applied, None
+
+
+# ---- merkle proofs: Txs.Hash / Txs.Proof (types/tx.go:30-75) ----
+
+@dataclass
+class MerkleProof:
+    """merkle.Proof (crypto/merkle/proof.go:26-31)."""
+    total: int
+    index: int
+    leaf_hash: bytes
+    aunts: List[bytes]
+
+
+def pack_items(items: List[bytes]):
+    """(data, leaf_off) of tmv_merkle_roots / tmv_merkle_proofs for `items`."""
+    import numpy as np
+    off = np.zeros(len(items) + 1, np.uint32)
+    off[1:] = np.cumsum([len(b) for b in items])
+    return np.frombuffer(b"".join(items), np.uint8), off
+
+
+def proofs_of_tree(total: int, leaf_hashes, aunt_off, aunts, first: int = 0) -> List[MerkleProof]:
+    """The proofs of one tree out of Context.merkle_proofs' arrays: leaves
+    [first, first + total)."""
+    return [MerkleProof(total, i, bytes(leaf_hashes[first + i]),
+                        [bytes(a) for a in aunts[int(aunt_off[first + i]):int(aunt_off[first + i + 1])]])
+            for i in range(total)]
+
+
+def txs_hash(ctx, txs: List[bytes]) -> bytes:
+    """Txs.Hash (types/tx.go:34-39): the merkle root over SHA-256(tx), the
+    transactions hashed on the device (TMV_MERKLE_PREHASH)."""
+    from . import _native
+    import numpy as np
+    data, off = pack_items(txs)
+    roots, _, _, _ = ctx.merkle_proofs(data, off, np.array([0, len(txs)], np.uint32),
+                                       flags=_native.TMV_MERKLE_PREHASH, aunts=False)
+    return bytes(roots[0])
+
+
+def txs_proofs(ctx, txs: List[bytes]) -> Tuple[bytes, List[MerkleProof]]:
+    """Txs.Proof (types/tx.go:61-70) for every transaction in one call: the
+    root and the merkle.Proof of each SHA-256(tx)."""
+    from . import _native
+    import numpy as np
+    data, off = pack_items(txs)
+    roots, leaves, aoff, aunts = ctx.merkle_proofs(data, off, np.array([0, len(txs)], np.uint32),
+                                                   flags=_native.TMV_MERKLE_PREHASH)
+    return bytes(roots[0]), proofs_of_tree(len(txs), leaves, aoff, aunts)
+

@@ -204,6 +204,15 @@ hipError_t launch_valset_hashes(const uint8_t *pk, const uint8_t *kind, const in
   return hipGetLastError();
 }
 
+// The leaf hashes alone (tmv_merkle_proofs for launches of short leaves).
+hipError_t launch_merkle_leaves(const uint8_t *data, const uint32_t *leaf_off, uint32_t n_leaves, uint32_t *node,
+                                hipStream_t stream) {
+  if (n_leaves)
+    hipLaunchKernelGGL(k_merkle_leaves, dim3((n_leaves + 255) / 256), dim3(256), 0, stream, data, leaf_off, n_leaves,
+                       node);
+  return hipGetLastError();
+}
+
 hipError_t launch_merkle_roots(const uint8_t *data, const uint32_t *leaf_off, uint32_t n_leaves,
                                const uint32_t *tree_off, uint32_t n_trees, uint32_t max_leaves, uint32_t *node_a,
                                uint32_t *node_b, uint8_t *out, hipStream_t stream) {

@@ -1413,6 +1413,11 @@ int tmv_kernel_timing_read(tmv_ctx *ctx, const char *kernel, double *total_ms, u
   else if (!strcmp(kernel, "k_prep_fused")) k = tmv::ktimer::kPrep;
   else if (!strcmp(kernel, "k_secp_prep")) k = tmv::ktimer::kSecpPrep;
   else if (!strcmp(kernel, "k_secp_verify")) k = tmv::ktimer::kSecpVerify;
+  else if (!strcmp(kernel, "k_merkle_leaves_long")) k = tmv::ktimer::kMerkleLeavesLong;
+  else if (!strcmp(kernel, "k_merkle_tree_levels")) k = tmv::ktimer::kMerkleTreeLevels;
+  else if (!strcmp(kernel, "k_merkle_aunts")) k = tmv::ktimer::kMerkleAunts;
+  else if (!strcmp(kernel, "k_merkle_verify_proofs")) k = tmv::ktimer::kMerkleVerify;
+  else if (!strcmp(kernel, "k_merkle_leaves")) k = tmv::ktimer::kMerkleLeaves;
   else { set_error("unknown timed kernel"); return TMV_ERR_ARG; }
   *total_ms = 0;
   *launches = 0;
@@ -2656,3 +2661,6 @@ int tmv_ed25519_verify_batch_device(tmv_ctx *ctx, int device, const uint8_t *d_p
 
 }  // extern "C"
 
+
+// tmv_merkle_proofs, tmv_merkle_verify_proofs, tmv_merkle_aunt_offsets
+#include "merkle_runtime.h"

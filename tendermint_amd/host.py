@@ -726,3 +726,166 @@ def verify_vote_batch(ctx, chain_id: str, votes: List[Vote], keys: List[Tuple[in
                                             ctypes.c_uint32, ctypes.POINTER(ctypes.c_int32)]
         L._tmhost_votes = True
     return verify_vote_batch_call(L.tmv_verify_vote_batch, ctx.handle, chain_id, votes, keys)
+
+
+# ---------------------------------------------------------------- block part sets and merkle proofs
+# tmv_part_set_headers / tmv_part_set_proofs / tmv_parts_verify / tmv_proofs_verify (include/tmhost.h):
+# NewPartSetFromData (types/part_set.go:172-200), PartSet.AddPart (types/part_set.go:272-300),
+# Proof.ValidateBasic + Proof.Verify (crypto/merkle/proof.go:52-117).
+PART_OK, PART_ERR_UNEXPECTED_INDEX, PART_ERR_INVALID_PROOF = 0, 1, 2
+ERR_STRIDE = 256
+
+
+@dataclass
+class Proof:
+    """merkle.Proof (crypto/merkle/proof.go:26-31)."""
+    total: int
+    index: int
+    leaf_hash: bytes
+    aunts: List[bytes] = field(default_factory=list)
+
+
+@dataclass
+class Part:
+    """types.Part (types/part_set.go:27-31)."""
+    index: int
+    bytes: bytes
+    proof: Proof
+
+
+class CProof(ctypes.Structure):
+    _fields_ = [("total", ctypes.c_int64), ("index", ctypes.c_int64), ("leaf_hash", CBytes),
+                ("aunts", ctypes.POINTER(CBytes)), ("n_aunts", ctypes.c_uint32)]
+
+
+class CPartIn(ctypes.Structure):
+    _fields_ = [("index", ctypes.c_uint32), ("bytes", CBytes), ("proof", CProof), ("set_total", ctypes.c_uint32),
+                ("set_hash", CBytes)]
+
+
+class CProofIn(ctypes.Structure):
+    _fields_ = [("proof", CProof), ("leaf", CBytes), ("root", CBytes)]
+
+
+def _ref_bytes(k: _Keep, b: bytes) -> CBytes:
+    """CBytes over b's own buffer (no copy; b is kept alive by k)."""
+    if not b:
+        return CBytes(None, 0)
+    k.refs.append(b)
+    return CBytes(ctypes.cast(ctypes.c_char_p(b), _u8p), len(b))
+
+
+def _c_proof(k: _Keep, p: Proof) -> CProof:
+    arr = (CBytes * max(1, len(p.aunts)))()
+    for i, a in enumerate(p.aunts):
+        arr[i] = _ref_bytes(k, a)
+    k.refs.append(arr)
+    return CProof(p.total, p.index, _ref_bytes(k, p.leaf_hash), arr, len(p.aunts))
+
+
+def _setup_merkle(L):
+    if not getattr(L, "_tmhost_merkle", False):
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        L.tmv_part_set_headers.argtypes = [ctypes.c_void_p, ctypes.POINTER(CBytes), ctypes.c_uint32, ctypes.c_uint32,
+                                           u32p, _u8p]
+        L.tmv_part_set_proofs.argtypes = [ctypes.c_void_p, ctypes.POINTER(CBytes), ctypes.c_uint32, ctypes.c_uint32,
+                                          u32p, _u8p, _u8p, u32p, _u8p, ctypes.c_uint64]
+        L.tmv_parts_verify.argtypes = [ctypes.c_void_p, ctypes.POINTER(CPartIn), ctypes.c_uint32,
+                                       ctypes.POINTER(ctypes.c_int32), ctypes.c_char_p, ctypes.c_size_t]
+        L.tmv_proofs_verify.argtypes = [ctypes.c_void_p, ctypes.POINTER(CProofIn), ctypes.c_uint32,
+                                        ctypes.POINTER(ctypes.c_int32), ctypes.c_char_p, ctypes.c_size_t]
+        L._tmhost_merkle = True
+    return L
+
+
+def _handle(ctx):
+    return ctx.handle if ctx is not None else None
+
+
+def _texts(results, errs, n):
+    raw = errs.raw
+    return [None if results[i] == 0 else raw[i * ERR_STRIDE:(i + 1) * ERR_STRIDE].split(b"\0", 1)[0].decode()
+            for i in range(n)]
+
+
+def part_set_headers(ctx, blocks: List[bytes], part_size: int, lib=None) -> List[Tuple[int, bytes]]:
+    """NewPartSetFromData(block, part_size).Header() of each block: (total, hash).
+    lib: the library to call (default libtmgpu.so; the CPU tests pass the
+    host layer built without the engine, with ctx = None)."""
+    L = _setup_merkle(lib or _native.lib())
+    k = _Keep()
+    n = len(blocks)
+    arr = (CBytes * max(1, n))()
+    for i, b in enumerate(blocks):
+        arr[i] = _ref_bytes(k, b)
+    totals = (ctypes.c_uint32 * max(1, n))()
+    hashes = (ctypes.c_uint8 * (32 * max(1, n)))()
+    rc = L.tmv_part_set_headers(_handle(ctx), arr, n, part_size, totals, ctypes.cast(hashes, _u8p))
+    if rc < 0:
+        raise NativeError(f"tmv_part_set_headers failed ({rc})")
+    return [(totals[i], bytes(hashes[32 * i:32 * i + 32])) for i in range(n)]
+
+
+def part_set_proofs(ctx, blocks: List[bytes], part_size: int, lib=None) -> List[Tuple[int, bytes, List[Proof]]]:
+    """As part_set_headers, with every part's merkle.Proof: (total, hash, proofs)."""
+    L = _setup_merkle(lib or _native.lib())
+    k = _Keep()
+    n = len(blocks)
+    arr = (CBytes * max(1, n))()
+    for i, b in enumerate(blocks):
+        arr[i] = _ref_bytes(k, b)
+    parts = sum((len(b) + part_size - 1) // part_size for b in blocks) if part_size > 0 else 0  # 0: the library's error
+    totals = (ctypes.c_uint32 * max(1, n))()
+    hashes = (ctypes.c_uint8 * (32 * max(1, n)))()
+    leaves = (ctypes.c_uint8 * (32 * max(1, parts)))()
+    aoff = (ctypes.c_uint32 * (parts + 1))()
+    cap = 32 * max(1, parts)
+    aunts = (ctypes.c_uint8 * (32 * cap))()
+    rc = L.tmv_part_set_proofs(_handle(ctx), arr, n, part_size, totals, ctypes.cast(hashes, _u8p),
+                               ctypes.cast(leaves, _u8p), aoff, ctypes.cast(aunts, _u8p), cap)
+    if rc < 0:
+        raise NativeError(f"tmv_part_set_proofs failed ({rc})")
+    out, p = [], 0
+    lv, av = bytes(leaves), bytes(aunts)
+    for b in range(n):
+        proofs = []
+        for i in range(totals[b]):
+            proofs.append(Proof(totals[b], i, lv[32 * p:32 * p + 32],
+                                [av[32 * a:32 * a + 32] for a in range(aoff[p], aoff[p + 1])]))
+            p += 1
+        out.append((totals[b], bytes(hashes[32 * b:32 * b + 32]), proofs))
+    return out
+
+
+def parts_verify(ctx, parts: List[Tuple[Part, int, bytes]], lib=None) -> List[Tuple[int, Optional[str]]]:
+    """PartSet.AddPart's checks for each (part, PartSetHeader.Total, PartSetHeader.Hash):
+    (PART_*, the reference's error text or None)."""
+    L = _setup_merkle(lib or _native.lib())
+    k = _Keep()
+    n = len(parts)
+    arr = (CPartIn * max(1, n))()
+    for i, (part, total, hash_) in enumerate(parts):
+        arr[i] = CPartIn(part.index, _ref_bytes(k, part.bytes), _c_proof(k, part.proof), total, _ref_bytes(k, hash_))
+    results = (ctypes.c_int32 * max(1, n))()
+    errs = ctypes.create_string_buffer(ERR_STRIDE * max(1, n))
+    rc = L.tmv_parts_verify(_handle(ctx), arr, n, results, errs, ERR_STRIDE)
+    if rc < 0:
+        raise NativeError(f"tmv_parts_verify failed ({rc})")
+    return list(zip(list(results)[:n], _texts(results, errs, n)))
+
+
+def proofs_verify(ctx, items: List[Tuple[Proof, bytes, bytes]], lib=None) -> List[Optional[str]]:
+    """Proof.ValidateBasic then Proof.Verify(root, leaf) of each (proof, leaf, root):
+    None or the reference's error text."""
+    L = _setup_merkle(lib or _native.lib())
+    k = _Keep()
+    n = len(items)
+    arr = (CProofIn * max(1, n))()
+    for i, (proof, leaf, root) in enumerate(items):
+        arr[i] = CProofIn(_c_proof(k, proof), _ref_bytes(k, leaf), _ref_bytes(k, root))
+    results = (ctypes.c_int32 * max(1, n))()
+    errs = ctypes.create_string_buffer(ERR_STRIDE * max(1, n))
+    rc = L.tmv_proofs_verify(_handle(ctx), arr, n, results, errs, ERR_STRIDE)
+    if rc < 0:
+        raise NativeError(f"tmv_proofs_verify failed ({rc})")
+    return _texts(results, errs, n)
