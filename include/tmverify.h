@@ -286,6 +286,14 @@ int tmv_kernel_timing_read(tmv_ctx *ctx, const char *kernel, double *total_ms, u
 /* Cumulative key-cache counters over the context's devices. */
 int tmv_key_cache_stats(tmv_ctx *ctx, uint64_t *hits, uint64_t *misses, uint32_t *used, uint32_t *capacity);
 
+/* Point cache (decoded ed25519 public keys, one table per device, used by
+ * uncached batch-equation launches; TMV_POINT_CACHE_SLOTS): keys served from
+ * the table and keys decoded, cumulative since the table was allocated and
+ * summed over the context's devices, and the capacity in slots.  The
+ * counters are read from the devices on this call only; the caller has
+ * waited for the launches it wants counted. */
+int tmv_point_cache_stats(tmv_ctx *ctx, uint64_t *hits, uint64_t *misses, uint32_t *slots);
+
 /* Library metrics (verifies/s, batch size, fallback count, H2D
  * bytes -- the reference exports its own per package through Prometheus,
  * e.g. internal/consensus/metrics.gen.go; a Go shim would publish these).

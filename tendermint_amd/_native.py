@@ -52,7 +52,7 @@ EXPORTS = [
     "tmv_ed25519_verify_batch", "tmv_ed25519_verify", "tmv_sr25519_verify_batch",
     "tmv_secp256k1_verify_batch", "tmv_secp256k1_verify",
     "tmv_verify_mixed_batch", "tmv_ed25519_verify_batch_device", "tmv_verify_mixed_batch_device",
-    "tmv_verify_batch_ex", "tmv_key_cache_stats", "tmv_set_batch_options", "tmv_batch_stats",
+    "tmv_verify_batch_ex", "tmv_key_cache_stats", "tmv_point_cache_stats", "tmv_set_batch_options", "tmv_batch_stats",
     "tmv_subgroup_stats", "tmv_validator_set_hashes",
     "tmv_verify_mixed_batch_ex", "tmv_verify_batch_device_ex", "tmv_verify_batches_device",
     "tmv_verify_votes", "tmv_vote_sign_bytes_device", "tmv_merkle_roots",
@@ -149,6 +149,8 @@ def lib() -> ctypes.CDLL:
                                           i8p]
         L.tmv_key_cache_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
                                           ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]
+        L.tmv_point_cache_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
+                                            ctypes.POINTER(ctypes.c_uint32)]
         L.tmv_set_batch_options.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, u8p, ctypes.c_uint32]
         L.tmv_batch_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
         L.tmv_kernel_timing.argtypes = [vp, ctypes.c_int]
@@ -513,6 +515,14 @@ class Context:
         self._check(self._lib.tmv_key_cache_stats(self._h, ctypes.byref(h), ctypes.byref(m), ctypes.byref(u),
                                                   ctypes.byref(c)), "tmv_key_cache_stats")
         return {"hits": h.value, "misses": m.value, "used": u.value, "capacity": c.value}
+
+    def point_cache_stats(self):
+        """Hits, misses and capacity of the devices' point caches (read from the devices now)."""
+        h, m = ctypes.c_uint64(), ctypes.c_uint64()
+        c = ctypes.c_uint32()
+        self._check(self._lib.tmv_point_cache_stats(self._h, ctypes.byref(h), ctypes.byref(m), ctypes.byref(c)),
+                    "tmv_point_cache_stats")
+        return {"hits": h.value, "misses": m.value, "slots": c.value}
 
     def metrics(self) -> dict:
         """tmv_metrics: cumulative counters (plus verifies_per_s_host, the

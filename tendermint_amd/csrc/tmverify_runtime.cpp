@@ -247,6 +247,11 @@ struct Device {
   std::vector<uint8_t> kseen;  // resolve_keys: slots found, per lookup part
   uint64_t kepoch = 0, khits = 0, kmisses = 0;
   DeviceBuf d_kbuild, h_kbuild;
+  // point cache (point_cache.h): decoded public keys, shared by every stream
+  // of the device; allocated at the first eligible launch (point_cache_view)
+  tmv::PointCache pc{nullptr, nullptr, 0, 0};
+  uint32_t pc_slots = 0;    // capacity (TMV_POINT_CACHE_SLOTS, rounded); 0 = off
+  bool pc_tried = false;    // the allocation was attempted (a failure leaves the path off)
   DeviceBuf d_valset, h_valset;  // tmv_validator_set_hashes staging
   uint32_t *d_secp_gtab = nullptr;             // secp256k1: j G, j = 1..15, affine (secp256k1.h)
   DeviceBuf d_secp_in, h_secp_in, d_secp_work; // tmv_secp256k1_verify_batch staging and workspace
@@ -334,6 +339,13 @@ int g_kernel_override = -1;  // A/B (TMV_KERNEL=quad|single): -1 auto, 0 single,
 // both.  Flags override per call.
 uint32_t g_msm_min = 32768;
 uint32_t g_km_min = 16384;
+// Point cache capacity in 64-byte slots (TMV_POINT_CACHE_SLOTS, rounded down
+// to a power of two; 0 = off): 2^21 slots (128 MiB).  A key has one slot, so
+// of a validator set of 10,000 keys the share that collides with another --
+// the steady-state misses -- is about 10,000 / 2^21 = 0.48 %
+// (tests/test_point_cache_hash.py counts it with the factory's keys: 72 of
+// 9,964, 0.72 %; random keys average 45).
+constexpr uint64_t kPointCacheSlots = 1ull << 21;
 uint32_t g_msm_chunk = 0;  // A/B (TMV_MSM_CHUNK): 16 or 32 overrides the chunk length
 uint32_t g_msm_parts = 0;  // A/B (TMV_MSM_PARTS): running-sum lanes per window (power of two <= H)
 // Key-cached batches up to this size run as one fused latency kernel
@@ -865,7 +877,33 @@ static int init_device(Device &d) {
   }
   const char *kc = getenv("TMV_KEY_CACHE_CAPACITY");
   d.kcap = kc ? (uint32_t)strtoul(kc, nullptr, 10) : 4096u;  // voi's LRU size (crypto/ed25519/ed25519.go:56)
+  const char *ps = getenv("TMV_POINT_CACHE_SLOTS");
+  d.pc_slots = tmv::pc_round_slots(ps ? strtoull(ps, nullptr, 10) : kPointCacheSlots);
   return 0;
+}
+
+// The device's point cache for a launch on stream s (table null: off).  The
+// table is allocated and zeroed at the first call; without room for it the
+// path stays off for this device, which is no error.  Caller holds d.mu.
+static tmv::PointCache point_cache_view(Device &d, hipStream_t s) {
+  if (!d.pc_tried && d.pc_slots) {
+    d.pc_tried = true;
+    const size_t tbytes = (size_t)d.pc_slots * tmv::kPcEntryWords * 4;
+    void *p = nullptr;
+    if (hipMalloc(&p, tbytes + 64) != hipSuccess) {
+      (void)hipGetLastError();
+    } else if (hipMemsetAsync(p, 0, tbytes + 64, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
+      (void)hipGetLastError();
+      (void)hipFree(p);
+    } else {
+      d.pc.table = static_cast<tmv::pc_quad *>(p);
+      d.pc.counters = reinterpret_cast<unsigned long long *>(static_cast<uint8_t *>(p) + tbytes);
+      d.pc.bucket_mask = d.pc_slots / tmv::kPcWays - 1;
+    }
+  }
+  tmv::PointCache v = d.pc;
+  v.min_n = tmv::point_cache_min();
+  return v;
 }
 
 // Resolve the key slot of every entry, building the comb tables of missing
@@ -1131,6 +1169,7 @@ static int batch_check(Device &d, const LaunchOpts &o, bool sr, const uint8_t *p
   if (!ws) return rc;
   tmv::Ed25519Work w = tmv::Ed25519Work::carve(ws->work.ptr, n);
   tmv::MsmWork mw = tmv::MsmWork::carve(ws->msm.ptr, n, o.p);
+  if (!sr && n >= tmv::point_cache_min()) w.pc = point_cache_view(d, s);
   hipError_t e;
   if (feed) {  // parts as their inputs land, then one tail
     const std::vector<uint32_t> b = stream_parts(n, o.p.m());
@@ -1444,6 +1483,12 @@ int tmv_internal_option(const char *name, int64_t value) {
     tmv::set_half_scalar_mode((int)value);
     return 0;
   }
+  // "point_cache_min": launches of at least `value` entries probe the point
+  // cache (0 restores the default), so that tests reach it with small batches
+  if (name && !strcmp(name, "point_cache_min")) {
+    tmv::set_point_cache_min(value < 0 ? 0u : (uint32_t)value);
+    return 0;
+  }
   set_error("unknown internal option");
   return TMV_ERR_ARG;
 }
@@ -1562,6 +1607,7 @@ void tmv_close(tmv_ctx *ctx) {
     d->h_kbuild.release();
     if (d->kt.tab) (void)hipFree(d->kt.tab);
     if (d->kt.ok) (void)hipFree(d->kt.ok);
+    if (d->pc.table) (void)hipFree(d->pc.table);
     if (d->d_bcomb) (void)hipFree(d->d_bcomb);
     if (d->d_prefix) (void)hipFree(d->d_prefix);
     if (d->d_btab_q) (void)hipFree(d->d_btab_q);
@@ -2267,6 +2313,51 @@ int tmv_key_cache_stats(tmv_ctx *ctx, uint64_t *hits, uint64_t *misses, uint32_t
   if (capacity) *capacity = c;
   return 0;
 }
+
+int tmv_point_cache_stats(tmv_ctx *ctx, uint64_t *hits, uint64_t *misses, uint32_t *slots) {
+  if (!ctx) return TMV_ERR_ARG;
+  uint64_t h = 0, m = 0;
+  uint32_t c = 0;
+  for (auto &d : ctx->devs) {
+    std::lock_guard<std::mutex> lk(d->mu);
+    c += d->pc_slots;
+    if (!d->pc.table) continue;
+    unsigned long long v[2];
+    hipError_t e = hipSetDevice(d->id);
+    if (e == hipSuccess) e = hipMemcpy(v, d->pc.counters, sizeof(v), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) { set_error("point cache counters", e); return TMV_ERR_NO_DEVICE; }
+    h += v[0]; m += v[1];
+  }
+  if (hits) *hits = h;
+  if (misses) *misses = m;
+  if (slots) *slots = c;
+  return 0;
+}
+
+#ifdef TMV_CHECKS
+// Test hooks of the checks build only: read and overwrite the point cache of
+// the context's first device (poisoning tests).  bytes = slots x 64.
+int tmv_internal_point_cache_read(tmv_ctx *ctx, uint8_t *out, uint64_t bytes) {
+  if (!ctx || !out || ctx->devs.empty()) return TMV_ERR_ARG;
+  Device &d = *ctx->devs[0];
+  std::lock_guard<std::mutex> lk(d.mu);
+  if (!d.pc.table || bytes != (uint64_t)d.pc_slots * 64) return TMV_ERR_ARG;
+  if (hipSetDevice(d.id) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+      hipMemcpy(out, d.pc.table, bytes, hipMemcpyDeviceToHost) != hipSuccess)
+    return TMV_ERR_NO_DEVICE;
+  return 0;
+}
+int tmv_internal_point_cache_write(tmv_ctx *ctx, const uint8_t *in, uint64_t bytes) {
+  if (!ctx || !in || ctx->devs.empty()) return TMV_ERR_ARG;
+  Device &d = *ctx->devs[0];
+  std::lock_guard<std::mutex> lk(d.mu);
+  if (!d.pc.table || bytes != (uint64_t)d.pc_slots * 64) return TMV_ERR_ARG;
+  if (hipSetDevice(d.id) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+      hipMemcpy(d.pc.table, in, bytes, hipMemcpyHostToDevice) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
+    return TMV_ERR_NO_DEVICE;
+  return 0;
+}
+#endif
 
 int tmv_metrics_read(tmv_ctx *ctx, tmv_metrics *out) {
   if (!ctx || !out) { set_error("null argument"); return TMV_ERR_ARG; }

@@ -4,6 +4,7 @@
 #include "curve25519.h"
 #include "merlin_dev.h"
 #include "msm.h"
+#include "point_cache.h"
 #include "../../include/tmverify.h"
 
 namespace tmv {
@@ -26,7 +27,14 @@ struct Ed25519Work {
   // instead of every lane of the entry's quad repeating the reduction
   uint32_t *hs;
   uint32_t *hs_buf;
-  static size_t bytes(uint32_t n) { return (size_t)n * (160 + 160 + 32 + 4 + 2560 + 48) + 256; }
+  // point cache (point_cache.h; pc.table null: off): the device's table, and
+  // the A lanes the probe pass could not serve -- entry indices, counted by
+  // miss_count[0].  A view starting at entry e0 (a multiple of 32) keeps its
+  // own count in miss_count[e0 / 32], since parts of a launch may run at once.
+  PointCache pc;
+  uint32_t *miss_list;   // n words
+  uint32_t *miss_count;  // n / 32 + 1 words
+  static size_t bytes(uint32_t n) { return (size_t)n * (160 + 160 + 32 + 4 + 2560 + 48 + 5) + 256 + 64; }
   // carve a workspace for n entries out of base (16-byte aligned pieces)
   static Ed25519Work carve(void *base, uint32_t n) {
     uint8_t *b = static_cast<uint8_t *>(base);
@@ -39,6 +47,10 @@ struct Ed25519Work {
     w.hs_buf = reinterpret_cast<uint32_t *>(b + ((356ull * n + 15) & ~15ull) + 2560ull * n);
     w.hs = nullptr;
     w.niels = nullptr;
+    w.pc = PointCache{nullptr, nullptr, 0, 0};
+    uint8_t *ml = b + ((356ull * n + 15) & ~15ull) + 2608ull * n;
+    w.miss_list = reinterpret_cast<uint32_t *>(ml);
+    w.miss_count = reinterpret_cast<uint32_t *>(ml + ((4ull * n + 15) & ~15ull));
     return w;
   }
 };
@@ -137,6 +149,18 @@ void set_half_scalar_mode(int mode);
 // Launches of at least this many entries use the located fallback
 // (TMV_LOCATE_MIN, 0 = never).
 uint32_t locate_min_entries();
+// Launches of at least this many entries probe the point cache
+// (point_cache.h); smaller ones keep the one-kernel prep.  The probe path
+// costs a 4-byte memset and a second kernel, about 80 us of launch chain, and
+// saves the A decodes: single C2 launches alone, cache off -> on (same box,
+// profiles/point_cache/alone.txt): 10k 0.75 -> 0.83 ms, 32,768 0.88 -> 0.96,
+// 65,536 1.12 -> 1.14, 125k 1.51 -> 1.48, 2.56M 19.2 -> 17.9.  The threshold
+// sits just under the 125k shard, above every size that lost.
+// set_point_cache_min is a test aid (tmv_internal_option "point_cache_min";
+// 0 restores the default).
+constexpr uint32_t kPointCacheMin = 120000;
+void set_point_cache_min(uint32_t n);
+uint32_t point_cache_min();
 // Whether a batch-equation launch of n entries with these parameters runs
 // the located fallback (tmv_metrics reads its counters).
 bool locate_enabled(uint32_t n, const MsmParams &p);

@@ -55,24 +55,10 @@ k_ed25519_verify(const uint8_t *__restrict__ pk, const uint8_t *__restrict__ sig
 
 // Decode blocks (lanes [0, m) decode A, [m, 2m) decode R) and hash blocks
 // (one lane per entry: SHA-512 + Barrett, or the merlin transcript).
+// The prep's outputs for one decoded point of entry e (A or R): its flag, its
+// Niels line for the batch equation, and -A (P3Q) or R (CachedQ / P3Q).
 template <bool SR>
-__device__ __forceinline__ void prep_decode_block(uint32_t bx, const uint8_t *__restrict__ pk,
-                                                  const uint8_t *__restrict__ sig, const uint32_t *__restrict__ idx,
-                                                  const uint32_t *count_ptr, uint32_t n, Ed25519Work w, int aligned) {
-  const uint32_t m = entry_count(count_ptr, n);
-  const uint32_t j = bx * blockDim.x + threadIdx.x;
-  if (j >= 2 * m) return;
-  const bool isA = j < m;
-  const uint32_t e = isA ? j : j - m;
-  const uint32_t i = idx ? idx[e] : e;
-  uint32_t p_w[8];
-  const uint8_t *src = isA ? pk + 32ull * i : sig + 64ull * i;
-  if (aligned) load_words_aligned(p_w, src);
-  else load_words_unaligned(p_w, src);
-  ge_p3 P;
-  bool ok;
-  if (SR) ok = ristretto_decode(P, p_w);
-  else ok = ge_decode_zip215(P, p_w);
+__device__ __forceinline__ void prep_store_point(uint32_t e, bool isA, bool ok, ge_p3 &P, const Ed25519Work &w) {
   if (!ok) ge_p3_identity(P);  // keep limbs bounded; the flag rejects the entry
   w.flags[4 * e + (isA ? 0 : 1)] = ok ? 1 : 0;
   if (w.niels) {  // -P in affine Niels form for the batch equation (Z = 1)
@@ -102,6 +88,27 @@ __device__ __forceinline__ void prep_decode_block(uint32_t bx, const uint8_t *__
     dst[2] = c.T2d;
     dst[3] = c.Z;
   }
+}
+
+template <bool SR>
+__device__ __forceinline__ void prep_decode_block(uint32_t bx, const uint8_t *__restrict__ pk,
+                                                  const uint8_t *__restrict__ sig, const uint32_t *__restrict__ idx,
+                                                  const uint32_t *count_ptr, uint32_t n, Ed25519Work w, int aligned) {
+  const uint32_t m = entry_count(count_ptr, n);
+  const uint32_t j = bx * blockDim.x + threadIdx.x;
+  if (j >= 2 * m) return;
+  const bool isA = j < m;
+  const uint32_t e = isA ? j : j - m;
+  const uint32_t i = idx ? idx[e] : e;
+  uint32_t p_w[8];
+  const uint8_t *src = isA ? pk + 32ull * i : sig + 64ull * i;
+  if (aligned) load_words_aligned(p_w, src);
+  else load_words_unaligned(p_w, src);
+  ge_p3 P;
+  bool ok;
+  if (SR) ok = ristretto_decode(P, p_w);
+  else ok = ge_decode_zip215(P, p_w);
+  prep_store_point<SR>(e, isA, ok, P, w);
 }
 
 template <bool SR>
@@ -157,6 +164,83 @@ k_prep_fused(const uint8_t *__restrict__ pk, const uint8_t *__restrict__ sig, co
              uint32_t n, Ed25519Work w, const strobe_t *__restrict__ prefix, int aligned, uint32_t dblocks) {
   if (blockIdx.x < dblocks) prep_decode_block<SR>(blockIdx.x, pk, sig, idx, count_ptr, n, w, aligned);
   else prep_hash_block<SR>(blockIdx.x - dblocks, pk, sig, msg, msg_off, idx, count_ptr, n, w, prefix, aligned);
+}
+
+// ---------------------------------------------------------------------------
+// The prep with the point cache (point_cache.h; ed25519 batch-equation
+// launches of contiguous entries).  k_prep_probe is k_prep_fused with the A
+// lanes replaced by probes: R blocks first (the long chains), then the hash
+// blocks, then the probe blocks.  A probe that passes the checked load writes
+// A's outputs; every other lane appends its entry to the launch's miss list
+// (a ballot and one atomic per wave), which k_prep_miss -- the next kernel on
+// the stream -- decodes densely, so that one miss does not make its 63
+// neighbours walk the square-root chain with it.
+__global__ void __launch_bounds__(kVerifyBlock)
+k_prep_probe(const uint8_t *__restrict__ pk, const uint8_t *__restrict__ sig, const uint8_t *__restrict__ msg,
+             const uint32_t *__restrict__ msg_off, uint32_t n, Ed25519Work w, int aligned, uint32_t rblocks,
+             uint32_t hblocks) {
+  if (blockIdx.x < rblocks) {
+    const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n) return;
+    uint32_t r_w[8];
+    if (aligned) load_words_aligned(r_w, sig + 64ull * e);
+    else load_words_unaligned(r_w, sig + 64ull * e);
+    ge_p3 P;
+    const bool ok = ge_decode_zip215(P, r_w);
+    prep_store_point<false>(e, false, ok, P, w);
+    return;
+  }
+  if (blockIdx.x < rblocks + hblocks) {
+    prep_hash_block<false>(blockIdx.x - rblocks, pk, sig, msg, msg_off, nullptr, nullptr, n, w, nullptr, aligned);
+    return;
+  }
+  const uint32_t e = (blockIdx.x - rblocks - hblocks) * blockDim.x + threadIdx.x;
+  const bool live = e < n;
+  bool hit = false;
+  if (live) {
+    uint32_t a_w[8];
+    if (aligned) load_words_aligned(a_w, pk + 32ull * e);
+    else load_words_unaligned(a_w, pk + 32ull * e);
+    ge_p3 P;
+    hit = pc_probe(P, w.pc.table, w.pc.bucket_mask, a_w);
+    if (hit) prep_store_point<false>(e, true, true, P, w);
+  }
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t hm = __ballot(hit), mm = __ballot(live && !hit);
+  uint32_t base = 0;
+  if (lane == 0) {  // counters and the miss list: once per wave
+    if (hm) atomicAdd(&w.pc.counters[0], (unsigned long long)__popcll(hm));
+    if (mm) {
+      atomicAdd(&w.pc.counters[1], (unsigned long long)__popcll(mm));
+      base = atomicAdd(w.miss_count, (uint32_t)__popcll(mm));
+    }
+  }
+  if (mm) {  // wave-uniform
+    base = __shfl(base, 0);
+    if (live && !hit) w.miss_list[base + __popcll(mm & ((1ull << lane) - 1))] = e;
+  }
+}
+
+// Decodes A of the entries on the miss list (one lane each) and inserts every
+// key that decodes; undecodable keys are never inserted.  The grid covers a
+// cold table (every entry missing); a block past the count returns at once
+// (block-uniform, as k_verify_quad_list's exit on fail_count).
+constexpr int kMissBlock = 64;
+__global__ void __launch_bounds__(kMissBlock)
+k_prep_miss(const uint8_t *__restrict__ pk, uint32_t n, Ed25519Work w, int aligned) {
+  const uint32_t cnt = min(*w.miss_count, n);
+  if (blockIdx.x * kMissBlock >= cnt) return;  // block-uniform
+  const uint32_t t = blockIdx.x * kMissBlock + threadIdx.x;
+  if (t >= cnt) return;
+  const uint32_t e = w.miss_list[t];
+  if (e >= n) return;  // cannot happen (the probe pass lists entries of this launch)
+  uint32_t a_w[8];
+  if (aligned) load_words_aligned(a_w, pk + 32ull * e);
+  else load_words_unaligned(a_w, pk + 32ull * e);
+  ge_p3 P;
+  const bool ok = ge_decode_zip215(P, a_w);
+  if (ok) pc_insert(w.pc.table, w.pc.bucket_mask, a_w, P.X);
+  prep_store_point<false>(e, true, ok, P, w);
 }
 
 constexpr int kQuadSigs = kQuadBlock / 4;
@@ -1088,16 +1172,40 @@ template hipError_t launch_quad_fallback<true>(const uint8_t *, const uint32_t *
                                                hipStream_t, const uint8_t *, const uint32_t *, const uint32_t *,
                                                const uint32_t *, const uint32_t *);
 
+// Launches of at least this many entries take the point cache (when the
+// launch carries one).  Test aid (tmv_internal_option "point_cache_min",
+// never set by a deployment): a lower bound so that small batches reach it.
+static std::atomic<uint32_t> g_point_cache_min{kPointCacheMin};
+void set_point_cache_min(uint32_t n) { g_point_cache_min = n ? n : kPointCacheMin; }
+uint32_t point_cache_min() { return g_point_cache_min.load(std::memory_order_relaxed); }
+
 template <bool SR>
 hipError_t launch_prep(const uint8_t *pk, const uint8_t *sig, const uint8_t *msg, const uint32_t *msg_off,
                        const uint32_t *idx, const uint32_t *count_ptr, uint32_t n, const strobe_t *prefix,
                        Ed25519Work w, int aligned, hipStream_t stream) {
   const uint32_t dblocks = (uint32_t)((2ull * n + kVerifyBlock - 1) / kVerifyBlock);
   const uint32_t hblocks = (n + kVerifyBlock - 1) / kVerifyBlock;
+  // point cache: ed25519 batch-equation launches of contiguous entries
+  const bool cached = !SR && w.niels && !idx && !count_ptr && w.pc.table && w.miss_list && n >= w.pc.min_n;
   void *tk = ktimer::begin(ktimer::kPrep, stream);
-  hipLaunchKernelGGL(k_prep_fused<SR>, dim3(dblocks + hblocks), dim3(kVerifyBlock), 0, stream, pk, sig, msg, msg_off,
-                     idx, count_ptr, n, w, prefix, aligned, dblocks);
-  const hipError_t e = hipGetLastError();
+  hipError_t e;
+  if (cached) {
+    e = hipMemsetAsync(w.miss_count, 0, sizeof(uint32_t), stream);
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(k_prep_probe, dim3(3 * hblocks), dim3(kVerifyBlock), 0, stream, pk, sig, msg, msg_off, n, w,
+                         aligned, hblocks, hblocks);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(k_prep_miss, dim3((n + kMissBlock - 1) / kMissBlock), dim3(kMissBlock), 0, stream, pk, n, w,
+                         aligned);
+      e = hipGetLastError();
+    }
+  } else {
+    hipLaunchKernelGGL(k_prep_fused<SR>, dim3(dblocks + hblocks), dim3(kVerifyBlock), 0, stream, pk, sig, msg, msg_off,
+                       idx, count_ptr, n, w, prefix, aligned, dblocks);
+    e = hipGetLastError();
+  }
   ktimer::end(tk, stream);
   return e;
 }

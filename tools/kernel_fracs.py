@@ -59,7 +59,9 @@ def launches(rows, key_fn):
         nm = short(r["Kernel_Name"])
         if nm.startswith("__amd") or nm.startswith("at::"):
             continue
-        if nm.startswith("k_prep"):
+        # a launch starts at its prep: k_prep_fused, or k_prep_probe with the
+        # point cache (k_prep_miss follows it inside the same launch)
+        if nm.startswith("k_prep") and not nm.startswith("k_prep_miss"):
             cur = {"_grid": int(r.get("Grid_Size_X") or r.get("Grid_Size")), "_span": [None, None]}
             out[cur["_grid"]].append(cur)
         if cur is None:
@@ -96,12 +98,14 @@ def main():
     isa = json.load(open(a.isa))["kernels"] if os.path.exists(a.isa) else {}
     shapes = [json.loads(x) for x in open(a.alone) if x.startswith("{")]
     # prep grid = ceil(2n / 256) + ceil(n / 256) blocks x 256 threads
+    # (with the point cache, k_prep_probe: 3 ceil(n / 256) blocks)
     grid_of = lambda n: (-(-2 * n // 256) + -(-n // 256)) * 256  # noqa: E731
+    grid_pc = lambda n: 3 * -(-n // 256) * 256  # noqa: E731
     res = {"peak_mul_per_s": peak, "source": {"trace": a.trace, "pmc": a.pmc or None, "isa": a.isa,
                                                "src_digest": a.src_digest or None}, "launches": []}
     for sh in shapes:
         n = sh["n"]
-        Ls = tl.get(grid_of(n), [])[a.skip:]
+        Ls = (tl.get(grid_of(n), []) + (tl.get(grid_pc(n), []) if grid_pc(n) != grid_of(n) else []))[a.skip:]
         if not Ls:
             continue
         m, c = bench.msm_shape(n, locate_min=a.locate_min)
@@ -121,7 +125,7 @@ def main():
                     d["algorithmic_products"] = int(p)
                     d["frac"] = round(p / (us * 1e-6) / peak, 4)
                     tot_prod += p
-            pls = pl.get(grid_of(n), [])[a.skip:]
+            pls = (pl.get(grid_of(n), []) + (pl.get(grid_pc(n), []) if grid_pc(n) != grid_of(n) else []))[a.skip:]
             if pls and nm in isa:
                 ops = statistics.median(L.get(nm, 0.0) for L in pls) * 64
                 share = isa[nm]["mad_share_of_int64"] or 0
