@@ -320,6 +320,52 @@ typedef struct {
 int tmv_proofs_verify(tmv_ctx *ctx, const tmv_proof_in *items, uint32_t n, int32_t *results, char *errs,
                       size_t err_stride);
 
+/* ---- blocks (types/block.go) ---- */
+/* Calls that hash at least $TMV_DEVICE_BLOCK_MIN commits (default 32, the rule
+ * of tmv_header_hashes) go to the device through
+ * tmv_commit_hashes / tmv_merkle_proofs / tmv_merkle_roots / tmv_header_hashes
+ * (weak references); smaller calls, and a build without the engine, compute
+ * on the host -- the same hashes, verdicts and texts either way. */
+
+/* Commit.Hash (types/block.go:900-918) of n commits; commits[i] == NULL is a
+ * nil commit (has_hash[i] = 0, hash_out + 32*i zeroed; has_hash may be NULL).
+ * On the device path every commit the engine accepts (flags <= 127, addresses
+ * of 0 or 20 bytes, signatures of at most 64) goes in one tmv_commit_hashes
+ * launch and the others are hashed on the host.  0 or < 0. */
+int tmv_commit_hash_many(tmv_ctx *ctx, const tmv_commit *const *commits, uint32_t n, uint8_t *hash_out,
+                         uint8_t *has_hash);
+
+/* The parts of a types.Block that Block.ValidateBasic reads.  evidence[i] is
+ * ev.Bytes() of evidence item i (EvidenceList.Hash, types/evidence.go: the
+ * merkle root over them); last_commit == NULL is a nil LastCommit. */
+typedef struct {
+  tmv_header header;
+  const tmv_bytes *txs;
+  uint32_t n_txs;
+  const tmv_bytes *evidence;
+  uint32_t n_evidence;
+  const tmv_commit *last_commit;
+} tmv_block;
+
+/* Block.ValidateBasic (types/block.go:53-94) of n blocks, in the reference's
+ * order and with its texts:
+ *   invalid header: <Header.ValidateBasic>
+ *   nil LastCommit
+ *   wrong LastCommit: <Commit.ValidateBasic>
+ *   wrong Header.LastCommitHash. Expected %X, got %X     (Commit.Hash)
+ *   wrong Header.DataHash. Expected %X, got %X           (Txs.Hash, types/tx.go:34-39)
+ *   wrong Header.EvidenceHash. Expected %X, got %X       (EvidenceList.Hash)
+ * The evidence items arrive encoded: their own ValidateBasic ("invalid
+ * evidence (#%d): ...", between the last two checks) is the caller's business
+ * and is not run here.  results[i] = 0 ok / 1 error, the text at
+ * errs + i*err_stride (errs may be NULL).  hash_out / has_hash (may be NULL):
+ * Header.Hash of each header as given, which is Block.Hash() of every block
+ * that passes (fillHeader changes nothing there).  A window on the device
+ * takes one launch per kind of hash; commits that fail Commit.ValidateBasic are
+ * not hashed.  Returns the number of failed blocks, or < 0. */
+int tmv_blocks_validate_basic(tmv_ctx *ctx, const tmv_block *blocks, uint32_t n, int32_t *results, char *errs,
+                              size_t err_stride, uint8_t *hash_out, uint8_t *has_hash);
+
 #ifdef __cplusplus
 }
 #endif

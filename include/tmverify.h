@@ -200,6 +200,26 @@ int tmv_validator_set_hashes(tmv_ctx *ctx, const uint8_t *pk, const uint8_t *key
  * < 0 on error. */
 int tmv_merkle_roots(tmv_ctx *ctx, const uint8_t *data, const uint32_t *leaf_off, uint32_t n_leaves,
                      const uint32_t *tree_off, uint32_t n_trees, uint8_t *hash_out);
+/* Commit.Hash of n_commits commits in one launch (types/block.go:900-918:
+ * merkle.HashFromByteSlices over the protobuf bytes of every CommitSig,
+ * proto/tendermint/types/types.pb.go:1764-1797), which Block.ValidateBasic
+ * compares with Header.LastCommitHash for every block blocksync applies
+ * (types/block.go:73-75).  Commit c holds the signatures [commit_off[c],
+ * commit_off[c+1]) in commit order; signature i: flag[i] (BlockIDFlag, at most
+ * 127: one varint byte), addr_len[i] (0 or 20) with the address at addr + 20*i
+ * (ignored when addr_len[i] is 0), the timestamp ts_seconds[i] / ts_nanos[i],
+ * sig_len[i] (0..64) with the signature at sig + 64*i.  Zero values are
+ * omitted as proto3 does; negative seconds or nanos take the 10-byte varint.
+ * Seconds outside [-62135596800, 253402300800) or nanos outside [0, 1e9) are
+ * outside the reference's domain (StdTimeMarshalTo fails and Commit.Hash
+ * panics); they are encoded as plain protobuf int64 / int32 here.
+ * hash_out: n_commits x 32 bytes (a commit without signatures hashes to
+ * SHA-256("")).  commit_off[0] must be 0.  Any other flag, addr_len or sig_len
+ * is TMV_ERR_ARG: the host layer hashes such commits itself.  Synchronous,
+ * device 0; at most 2^26 signatures per call; 0 or < 0 on error. */
+int tmv_commit_hashes(tmv_ctx *ctx, const uint8_t *flag, const uint8_t *addr_len, const uint8_t *addr,
+                      const int64_t *ts_seconds, const int32_t *ts_nanos, const uint8_t *sig_len, const uint8_t *sig,
+                      const uint32_t *commit_off, uint32_t n_commits, uint8_t *hash_out);
 
 /* Merkle inclusion proofs (crypto/merkle/proof.go).  Blocksync's replay loop
  * builds every block's part set (internal/blocksync/reactor.go:563-582:
@@ -275,7 +295,7 @@ int tmv_verify_mixed_batch_ex(tmv_ctx *ctx, uint32_t flags, const uint8_t *kind,
  * bucket sums), "k_msm_wpart" (window running sums), "k_prep_fused" (decode +
  * challenge), "k_secp_prep" and "k_secp_verify" (secp256k1), "k_merkle_leaves_long",
  * "k_merkle_leaves", "k_merkle_tree_levels", "k_merkle_aunts" and "k_merkle_verify_proofs" (the launches
- * of tmv_merkle_proofs / tmv_merkle_verify_proofs) -- is bracketed by HIP timing events on the stream it runs on
+ * of tmv_merkle_proofs / tmv_merkle_verify_proofs), "k_commit_leaves" (tmv_commit_hashes) -- is bracketed by HIP timing events on the stream it runs on
  * (process-wide, two event records per launch); 0 turns it off.
  * tmv_kernel_timing_read waits for the recorded launches of `kernel`, returns
  * their summed duration and count, and forgets them.  No reference

@@ -56,13 +56,14 @@ EXPORTS = [
     "tmv_subgroup_stats", "tmv_validator_set_hashes",
     "tmv_verify_mixed_batch_ex", "tmv_verify_batch_device_ex", "tmv_verify_batches_device",
     "tmv_verify_votes", "tmv_vote_sign_bytes_device", "tmv_merkle_roots",
-    "tmv_merkle_aunt_offsets", "tmv_merkle_proofs", "tmv_merkle_verify_proofs",
+    "tmv_merkle_aunt_offsets", "tmv_merkle_proofs", "tmv_merkle_verify_proofs", "tmv_commit_hashes",
     "tmv_kernel_timing", "tmv_kernel_timing_read", "tmv_metrics_read", "tmv_metrics_reset",
     # include/tmhost.h
     "tmv_batch_new", "tmv_batch_add", "tmv_batch_len", "tmv_batch_verify", "tmv_batch_free",
     "tmv_vote_sign_bytes", "tmv_vote_template_encode", "tmv_verify_commit", "tmv_verify_commits",
     "tmv_header_hashes", "tmv_light_verify_many", "tmv_light_verify", "tmv_verify_vote_batch",
     "tmv_part_set_headers", "tmv_part_set_proofs", "tmv_parts_verify", "tmv_proofs_verify",
+    "tmv_commit_hash_many", "tmv_blocks_validate_basic",
 ]
 
 
@@ -162,6 +163,8 @@ def lib() -> ctypes.CDLL:
         L.tmv_verify_mixed_batch_ex.argtypes = [vp, ctypes.c_uint32, u8p, u8p, u8p, u8p, u32p, ctypes.c_uint32, i8p]
         L.tmv_merkle_roots.argtypes = [vp, u8p, u32p, ctypes.c_uint32, u32p, ctypes.c_uint32, u8p]
         L.tmv_merkle_aunt_offsets.argtypes = [u32p, ctypes.c_uint32, u32p]
+        L.tmv_commit_hashes.argtypes = [vp, u8p, u8p, u8p, ctypes.POINTER(ctypes.c_int64),
+                                        ctypes.POINTER(ctypes.c_int32), u8p, u8p, u32p, ctypes.c_uint32, u8p]
         L.tmv_merkle_proofs.argtypes = [vp, ctypes.c_uint32, u8p, u32p, ctypes.c_uint32, u32p, ctypes.c_uint32, u8p,
                                         u8p, u32p, u8p]
         i64p = ctypes.POINTER(ctypes.c_int64)
@@ -423,6 +426,29 @@ class Context:
                                                        _p(set_off, ctypes.c_uint32), n_sets, _p(out)),
                     "tmv_validator_set_hashes")
         return out[:n_sets]
+
+    def commit_hashes(self, flag: np.ndarray, addr_len: np.ndarray, addr: np.ndarray, ts_seconds: np.ndarray,
+                      ts_nanos: np.ndarray, sig_len: np.ndarray, sig: np.ndarray,
+                      commit_off: np.ndarray) -> np.ndarray:
+        """Commit.Hash of each commit (tmv_commit_hashes): (n_commits, 32) uint8.
+        One entry per CommitSig: flag, addr_len (0 or 20), addr (n, 20),
+        ts_seconds, ts_nanos, sig_len (0..64), sig (n, 64); commit c holds the
+        signatures [commit_off[c], commit_off[c+1])."""
+        n_commits = len(commit_off) - 1
+        out = np.zeros((max(n_commits, 1), 32), np.uint8)
+
+        def col(a, dtype, width=1):
+            a = np.ascontiguousarray(a, dtype)
+            return a if a.size else np.zeros(width, dtype)
+        flag, addr_len, sig_len = col(flag, np.uint8), col(addr_len, np.uint8), col(sig_len, np.uint8)
+        addr, sig = col(addr, np.uint8, 20), col(sig, np.uint8, 64)
+        ts_seconds, ts_nanos = col(ts_seconds, np.int64), col(ts_nanos, np.int32)
+        commit_off = np.ascontiguousarray(commit_off, np.uint32)
+        self._check(self._lib.tmv_commit_hashes(self._h, _p(flag), _p(addr_len), _p(addr),
+                                                _p(ts_seconds, ctypes.c_int64), _p(ts_nanos, ctypes.c_int32),
+                                                _p(sig_len), _p(sig), _p(commit_off, ctypes.c_uint32), n_commits,
+                                                _p(out)), "tmv_commit_hashes")
+        return out[:n_commits]
 
     def merkle_roots(self, data, leaf_off: np.ndarray, tree_off: np.ndarray) -> np.ndarray:
         """merkle.HashFromByteSlices of each tree (tmv_merkle_roots): (n_trees, 32) uint8.

@@ -298,6 +298,109 @@ def blocksync_replay(ctx, chain_id: str, vals: H.ValidatorSet, blocks: List[Bloc
     return applied, None
 
 
+def _block_id_string(b: H.BlockID) -> str:
+    """BlockID.String (types/block.go:1413-1415, part_set.go:100-102)."""
+    return "%s:%d:%s" % (b.hash.hex().upper(), b.psh_total, (b.psh_hash + b"\0" * 6)[:6].hex().upper())
+
+
+def blocksync_replay_full(ctx, chain_id: str, vals: H.ValidatorSet, blocks: List[H.FullBlock],
+                          last_block_id: H.BlockID, initial_height: int = 1, window: int = 600,
+                          depth: Optional[int] = None, part_size: int = 65536, verify_commits=None, lib=None,
+                          vals_hash: Optional[bytes] = None, last_block_height: int = 0
+                          ) -> Tuple[int, Optional[Tuple[int, str]]]:
+    """poolRoutine's checks for each block pair (first, second)
+    (internal/blocksync/reactor.go:563-586) over a static validator set, with
+    nothing taken on trust from the caller: per window of `window` blocks
+      * firstID = BlockID{first.Hash(), first.MakePartSet(part_size).Header()}:
+        the hash from tmv_blocks_validate_basic (Header.Hash on the device),
+        the part-set header from `raw` through tmv_part_set_headers (a block
+        without `raw` is a ValueError);
+      * vals.VerifyCommitLight(chainID, firstID, first.Height, second.LastCommit);
+      * validateBlock(first) (internal/state/validation.go:14-96), in its order:
+        Block.ValidateBasic (the three header hashes recomputed on the device),
+        wrong Block.Header.ChainID, wrong Block.Header.Height, wrong
+        Block.Header.LastBlockID, wrong Block.Header.ValidatorsHash, wrong
+        Block.Header.NextValidatorsHash (both against the static set's hash,
+        computed once, or `vals_hash`), then at the initial height "initial
+        block can't have LastCommit signatures", else vals.VerifyCommit(chainID,
+        state.LastBlockID, first.Height-1, first.LastCommit).
+    state.LastBlockID is `last_block_id` and state.LastBlockHeight
+    `last_block_height` before the first block, and the previous block's
+    afterwards (ApplyBlock).  Left to the caller, because they need
+    application state or the wall clock: Block.Header.Version, AppHash,
+    ConsensusHash and LastResultsHash, the proposer check
+    (Validators.HasAddress), the block time checks, the evidence's own
+    ValidateBasic and its size limit.
+    `depth` windows in flight (in_order; default 2 on the engine, 1 with a
+    caller's `verify_commits`, a function jobs -> per-job error or None);
+    `lib`: the host layer to call (the CPU tests pass a build without the
+    engine, with ctx = None).  Returns (blocks applied, (height, error) or
+    None); the first error is the one the one-at-a-time loop returns."""
+    for b in blocks[:-1]:
+        if b.raw is None:
+            raise ValueError("blocksync_replay_full: block %d has no raw bytes" % b.height)
+    if depth is None:
+        depth = 1 if verify_commits else 2
+    if vals_hash is None:
+        vals_hash = validator_set_hashes(ctx, [vals])[0]
+    check = verify_commits or (lambda jobs: H.verify_commits(ctx, jobs))
+
+    def run(lo):
+        # the previous block rides along: its BlockID is state.LastBlockID of the window's first block
+        first_of = max(lo - 1, 0)
+        firsts = blocks[first_of:min(lo + window, len(blocks) - 1)]
+        basic = H.blocks_validate_basic(ctx, firsts, lib)
+        psh = H.part_set_headers(ctx, [b.raw for b in firsts], part_size, lib)
+        ids = [H.BlockID(hash_ or b"", total, phash) for (_, hash_), (total, phash) in zip(basic, psh)]
+        out, jobs, slots = [], [], []
+        for i in range(lo - first_of, len(firsts)):
+            first, second = firsts[i], blocks[first_of + i + 1]
+            g = first_of + i
+            state_last = ids[i - 1] if g > 0 else last_block_id
+            state_height = blocks[g - 1].height if g > 0 else last_block_height
+            hd = first.header
+            err = basic[i][0]
+            if err is None and hd.chain_id != chain_id:
+                err = "wrong Block.Header.ChainID. Expected %s, got %s" % (chain_id, hd.chain_id)
+            if err is None and state_height == 0 and hd.height != initial_height:
+                err = "wrong Block.Header.Height. Expected %d for initial block, got %d" % (hd.height, initial_height)
+            if err is None and state_height > 0 and hd.height != state_height + 1:
+                err = "wrong Block.Header.Height. Expected %d, got %d" % (state_height + 1, hd.height)
+            if err is None and not hd.last_block_id.equals(state_last):
+                err = "wrong Block.Header.LastBlockID.  Expected %s, got %s" % (_block_id_string(state_last),
+                                                                              _block_id_string(hd.last_block_id))
+            if err is None and hd.validators_hash != vals_hash:
+                err = "wrong Block.Header.ValidatorsHash.  Expected %s, got %s" % (vals_hash.hex().upper(),
+                                                                                 hd.validators_hash.hex().upper())
+            if err is None and hd.next_validators_hash != vals_hash:
+                err = "wrong Block.Header.NextValidatorsHash.  Expected %s, got %s" % (
+                    vals_hash.hex().upper(), hd.next_validators_hash.hex().upper())
+            light = len(jobs)
+            jobs.append(H.CommitJob(H.MODE_LIGHT, chain_id, vals, ids[i], hd.height, second.last_commit))
+            full = None
+            if err is None:
+                if hd.height == initial_height:
+                    if first.last_commit.signatures:
+                        err = "initial block can't have LastCommit signatures"
+                else:
+                    full = len(jobs)
+                    jobs.append(H.CommitJob(H.MODE_FULL, chain_id, vals, state_last, hd.height - 1,
+                                            first.last_commit))
+            out.append(hd.height)
+            slots.append((light, err, full))
+        res = check(jobs)
+        return [(h, res[light] or err or (res[full] if full is not None else None))
+                for h, (light, err, full) in zip(out, slots)]
+
+    applied = 0
+    for res in in_order(range(0, len(blocks) - 1, window), run, depth):
+        for height, err in res:
+            if err is not None:
+                return applied, (height, err)
+            applied += 1
+    return applied, None
+
+
 # ---- merkle proofs: Txs.Hash / Txs.Proof (types/tx.go:30-75) ----
 
 @dataclass

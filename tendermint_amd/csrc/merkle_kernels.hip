@@ -222,6 +222,11 @@ hipError_t launch_merkle_roots(const uint8_t *data, const uint32_t *leaf_off, ui
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
+  return launch_merkle_tree(tree_off, n_trees, max_leaves, node_a, node_b, out, stream);
+}
+
+hipError_t launch_merkle_tree(const uint32_t *tree_off, uint32_t n_trees, uint32_t max_leaves, uint32_t *node_a,
+                              uint32_t *node_b, uint8_t *out, hipStream_t stream) {
   if (!n_trees) return hipGetLastError();
   // small trees (Header.Hash: 14 leaves) take one wave per tree
   if (max_leaves <= 128)

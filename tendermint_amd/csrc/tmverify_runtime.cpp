@@ -1457,6 +1457,7 @@ int tmv_kernel_timing_read(tmv_ctx *ctx, const char *kernel, double *total_ms, u
   else if (!strcmp(kernel, "k_merkle_aunts")) k = tmv::ktimer::kMerkleAunts;
   else if (!strcmp(kernel, "k_merkle_verify_proofs")) k = tmv::ktimer::kMerkleVerify;
   else if (!strcmp(kernel, "k_merkle_leaves")) k = tmv::ktimer::kMerkleLeaves;
+  else if (!strcmp(kernel, "k_commit_leaves")) k = tmv::ktimer::kCommitLeaves;
   else { set_error("unknown timed kernel"); return TMV_ERR_ARG; }
   *total_ms = 0;
   *launches = 0;
@@ -2755,3 +2756,6 @@ int tmv_ed25519_verify_batch_device(tmv_ctx *ctx, int device, const uint8_t *d_p
 
 // tmv_merkle_proofs, tmv_merkle_verify_proofs, tmv_merkle_aunt_offsets
 #include "merkle_runtime.h"
+
+// tmv_commit_hashes
+#include "commit_runtime.h"

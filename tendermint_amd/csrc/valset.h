@@ -23,6 +23,11 @@ hipError_t launch_merkle_roots(const uint8_t *data, const uint32_t *leaf_off, ui
                                const uint32_t *tree_off, uint32_t n_trees, uint32_t max_leaves, uint32_t *node_a,
                                uint32_t *node_b, uint8_t *out, hipStream_t stream);
 
+// k_merkle_tree alone: the roots of n_trees trees whose leaf hashes are in
+// node_a (launch_merkle_roots' second step; Commit.Hash's, commit_kernels.hip).
+hipError_t launch_merkle_tree(const uint32_t *tree_off, uint32_t n_trees, uint32_t max_leaves, uint32_t *node_a,
+                              uint32_t *node_b, uint8_t *out, hipStream_t stream);
+
 // k_merkle_leaves alone: the leaf hashes of launch_merkle_roots into node.
 hipError_t launch_merkle_leaves(const uint8_t *data, const uint32_t *leaf_off, uint32_t n_leaves, uint32_t *node,
                                 hipStream_t stream);

@@ -889,3 +889,100 @@ def proofs_verify(ctx, items: List[Tuple[Proof, bytes, bytes]], lib=None) -> Lis
     if rc < 0:
         raise NativeError(f"tmv_proofs_verify failed ({rc})")
     return _texts(results, errs, n)
+
+
+# ---------------------------------------------------------------- blocks
+# tmv_commit_hash_many / tmv_blocks_validate_basic (include/tmhost.h): Commit.Hash
+# (types/block.go:900-918) and Block.ValidateBasic (types/block.go:53-94).
+
+class CBlock(ctypes.Structure):
+    _fields_ = [("header", CHeader), ("txs", ctypes.POINTER(CBytes)), ("n_txs", ctypes.c_uint32),
+                ("evidence", ctypes.POINTER(CBytes)), ("n_evidence", ctypes.c_uint32),
+                ("last_commit", ctypes.POINTER(CCommit))]
+
+
+@dataclass
+class FullBlock:
+    """The parts of a types.Block that blocksync's checks read: the header, the
+    transactions, the evidence list (ev.Bytes() of each item), the last commit
+    and, optionally, the serialised block as received (its part set)."""
+    header: Header
+    txs: List[bytes] = field(default_factory=list)
+    evidence: List[bytes] = field(default_factory=list)
+    last_commit: Optional[Commit] = None
+    raw: Optional[bytes] = None
+
+    @property
+    def height(self) -> int:
+        return self.header.height
+
+
+def _setup_blocks(L):
+    if not getattr(L, "_tmhost_blocks", False):
+        L.tmv_commit_hash_many.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.POINTER(CCommit)), ctypes.c_uint32,
+                                           _u8p, _u8p]
+        L.tmv_blocks_validate_basic.argtypes = [ctypes.c_void_p, ctypes.POINTER(CBlock), ctypes.c_uint32,
+                                                ctypes.POINTER(ctypes.c_int32), ctypes.c_char_p, ctypes.c_size_t,
+                                                _u8p, _u8p]
+        L._tmhost_blocks = True
+    return L
+
+
+def commit_hashes(ctx, commits: List[Optional[Commit]], lib=None) -> List[Optional[bytes]]:
+    """Commit.Hash of each commit (None for a nil commit).  lib: the library to
+    call (default libtmgpu.so; the CPU tests pass the host layer built without
+    the engine, with ctx = None)."""
+    L = _setup_blocks(lib or _native.lib())
+    k = _Keep()
+    n = len(commits)
+    arr = (ctypes.POINTER(CCommit) * max(1, n))()
+    for i, c in enumerate(commits):
+        if c is not None:
+            arr[i] = ctypes.pointer(_c_commit(k, c))
+    out = (ctypes.c_uint8 * (32 * max(1, n)))()
+    has = (ctypes.c_uint8 * max(1, n))()
+    rc = L.tmv_commit_hash_many(_handle(ctx), arr, n, ctypes.cast(out, _u8p), ctypes.cast(has, _u8p))
+    if rc < 0:
+        raise NativeError(f"tmv_commit_hash_many failed ({rc})")
+    return [bytes(out[32 * i:32 * i + 32]) if has[i] else None for i in range(n)]
+
+
+class PreparedBlocks:
+    """tmv_block[] for a list of FullBlock, built once (on the caller's thread;
+    the engine call may run on another)."""
+
+    def __init__(self, blocks: List[FullBlock]):
+        self.keep = k = _Keep()
+        self.n = n = len(blocks)
+        self.arr = (CBlock * max(1, n))()
+        for i, b in enumerate(blocks):
+            txs = (CBytes * max(1, len(b.txs)))()
+            for j, t in enumerate(b.txs):
+                txs[j] = _ref_bytes(k, t)
+            evs = (CBytes * max(1, len(b.evidence)))()
+            for j, e in enumerate(b.evidence):
+                evs[j] = _ref_bytes(k, e)
+            k.refs += [txs, evs]
+            lc = ctypes.pointer(_c_commit(k, b.last_commit)) if b.last_commit is not None else None
+            self.arr[i] = CBlock(_c_header(k, b.header), txs, len(b.txs), evs, len(b.evidence), lc)
+        self.results = (ctypes.c_int32 * max(1, n))()
+        self.errs = ctypes.create_string_buffer(ERR_STRIDE * max(1, n))
+        self.hashes = (ctypes.c_uint8 * (32 * max(1, n)))()
+        self.has = (ctypes.c_uint8 * max(1, n))()
+
+    def run(self, ctx, lib=None) -> List[Tuple[Optional[str], Optional[bytes]]]:
+        L = _setup_blocks(lib or _native.lib())
+        rc = L.tmv_blocks_validate_basic(_handle(ctx), self.arr, self.n, self.results, self.errs, ERR_STRIDE,
+                                         ctypes.cast(self.hashes, _u8p), ctypes.cast(self.has, _u8p))
+        if rc < 0:
+            raise NativeError(f"tmv_blocks_validate_basic failed ({rc})")
+        texts = _texts(self.results, self.errs, self.n)
+        raw = bytes(self.hashes)
+        return [(texts[i], raw[32 * i:32 * i + 32] if self.has[i] else None) for i in range(self.n)]
+
+
+def blocks_validate_basic(ctx, blocks: List[FullBlock], lib=None) -> List[Tuple[Optional[str], Optional[bytes]]]:
+    """Block.ValidateBasic of each block: (the reference's error text or None,
+    Header.Hash of the header as given, which is Block.Hash() of a block that
+    passes, or None where the reference returns nil)."""
+    return PreparedBlocks(blocks).run(ctx, lib)
