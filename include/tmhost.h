@@ -172,6 +172,40 @@ typedef struct {
 int tmv_verify_vote_batch(tmv_ctx *ctx, const char *chain_id, const tmv_vote_in *votes, uint32_t n,
                           int32_t *results);
 
+/* ---- vote extensions ---- */
+/* types.VoteExtensionSignBytes (types/vote.go:159-172) for (chain_id, height,
+ * round, extension).  Returns the length; writes min(len, cap) bytes. */
+size_t tmv_vote_extension_sign_bytes(const char *chain_id, int64_t height, int32_t round,
+                                     const uint8_t *ext, size_t ext_len, uint8_t *out, size_t cap);
+/* The template of tmv_verify_votes_and_extensions (tmverify.h): the bytes the
+ * extension messages of one (chain_id, height, round) share.  Returns the
+ * length; writes min(len, cap) bytes. */
+size_t tmv_vote_extension_template_encode(const char *chain_id, int64_t height, int32_t round, uint8_t *out, size_t cap);
+
+typedef struct { tmv_vote_in vote; const uint8_t *extension; uint32_t extension_len;
+                 const uint8_t *extension_signature; uint32_t extension_signature_len; } tmv_ext_vote_in;
+#define TMV_VOTE_MODE_VERIFY 0                /* Vote.Verify                 types/vote.go:240-243 */
+#define TMV_VOTE_MODE_VERIFY_AND_EXTENSION 1  /* Vote.VerifyVoteAndExtension types/vote.go:249-262 */
+#define TMV_VOTE_MODE_EXTENSION 2             /* Vote.VerifyExtension        types/vote.go:266-276 (no address check) */
+/* The three ways the reference verifies a vote that may carry an extension, n
+ * votes at once, in its order: the address check, the vote signature, then --
+ * for non-nil precommits only -- the extension signature over
+ * VoteExtensionSignBytes (an extension on a prevote or a nil precommit is not
+ * looked at; an extension signature that is empty or not 64 bytes long is an
+ * invalid signature).  results[i] = TMV_VOTE_*, identical to verifying vote i
+ * alone; failed_sig[i] (may be NULL) = 0 none, 1 the vote's, 2 the
+ * extension's.  All ed25519 signatures of the call, votes' and extensions',
+ * go out in one engine call with TMV_FLAG_KEY_CACHE, all sr25519 ones in
+ * another; secp256k1 ones (33-byte keys, address RIPEMD160(SHA256(key)))
+ * through tmv_secp256k1_verify_batch.  Calls with at least
+ * TMV_VOTE_EXT_DEVICE_MIN signatures of a kind (environment; default below)
+ * build that kind's messages on the device (tmv_verify_votes_and_extensions),
+ * smaller ones on the host (tmv_verify_batch_ex).  Returns the number of
+ * failed votes, or < 0 on an infrastructure error. */
+#define TMV_VOTE_EXT_DEVICE_MIN_DEFAULT 0xffffffffu /* host-built messages: measured faster at 300 .. 210,000 signatures per call, DESIGN.md section 17 */
+int tmv_verify_extended_votes(tmv_ctx *ctx, int mode, const char *chain_id, const tmv_ext_vote_in *votes, uint32_t n,
+                              int32_t *results /* TMV_VOTE_* */, uint8_t *failed_sig /* may be NULL: 0 none, 1 vote, 2 extension */);
+
 /* ---- light client (light/verifier.go) ---- */
 typedef struct {
   const uint8_t *p;

@@ -425,6 +425,34 @@ int64_t tmv_vote_sign_bytes_device(tmv_ctx *ctx, const tmv_vote_template *tmpl, 
                                    const tmv_vote *votes, uint32_t n, uint8_t *msg_out, size_t msg_cap,
                                    uint32_t *msg_off_out);
 
+/* ---- Vote extensions ----
+ * With vote extensions enabled a non-nil precommit carries a second
+ * signature of the same key, over VoteExtensionSignBytes
+ * (types/vote.go:159-172): CanonicalVoteExtension{extension, height, round,
+ * chain_id}, length-delimited,
+ *   M    = uvarint(len(body)) || body
+ *   body = [0x0a uvarint(E) ext] || tail
+ *   tail = [0x11 le64(height)] [0x19 le64(round)] [0x22 uvarint(C) chain_id]
+ * (proto3: zero / empty fields omitted).  tail is shared by the precommits of
+ * one (chain_id, height, round): the template, see
+ * tmv_vote_extension_template_encode in tmhost.h. */
+typedef struct tmv_vote_ext_template { const uint8_t *tail; uint32_t tail_len; } tmv_vote_ext_template;
+
+/* tmv_verify_votes plus extension entries in ONE batch: entries [0, n_votes) sign the vote messages of votes[]
+ * (exactly as tmv_verify_votes), entries [n_votes, n_votes + n_exts) sign the extension message built from
+ * etmpl[ext_tmpl[j]] and ext_data[ext_off[j] .. ext_off[j+1]).  pk / sig / status_out hold n_votes + n_exts
+ * entries in that order.  Either count may be 0.  Flags, statuses, return values, limits as tmv_verify_votes;
+ * TMV_ERR_ARG for ext_off[0] != 0, decreasing offsets, a template index out of range, a null segment. */
+int tmv_verify_votes_and_extensions(tmv_ctx *ctx, uint8_t key_kind, uint32_t flags,
+        const tmv_vote_template *tmpl, uint32_t n_tmpl, const tmv_vote *votes, uint32_t n_votes,
+        const tmv_vote_ext_template *etmpl, uint32_t n_etmpl, const uint32_t *ext_tmpl,
+        const uint8_t *ext_data, const uint32_t *ext_off, uint32_t n_exts,
+        const uint8_t *pk, const uint8_t *sig, int8_t *status_out);
+/* The extension messages as the device writes them, copied back (tests, tools); as tmv_vote_sign_bytes_device. */
+int64_t tmv_vote_extension_sign_bytes_device(tmv_ctx *ctx, const tmv_vote_ext_template *etmpl, uint32_t n_etmpl,
+        const uint32_t *ext_tmpl, const uint8_t *ext_data, const uint32_t *ext_off, uint32_t n_exts,
+        uint8_t *msg_out, size_t msg_cap, uint32_t *msg_off_out);
+
 #ifdef __cplusplus
 }
 #endif

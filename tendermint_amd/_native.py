@@ -42,6 +42,8 @@ TMV_MERKLE_SHORT_LEAVES = 8
 TMV_KIND_MIXED = 2
 TMV_KIND_SECP256K1 = 3  # include/tmhost.h: 33-byte compressed keys, verified signature by signature
 TMV_VOTE_WITH_BLOCK = 0x80000000
+# kVoteExtWaveMin (csrc/vote_ext.h): extension payloads from this length on are copied by the whole wave
+VOTE_EXT_WAVE_MIN = 96
 
 # tmv_vote (include/tmverify.h), 16 bytes
 VOTE_DTYPE = np.dtype([("ts_seconds", "<i8"), ("ts_nanos", "<i4"), ("tmpl", "<u4")])
@@ -55,7 +57,8 @@ EXPORTS = [
     "tmv_verify_batch_ex", "tmv_key_cache_stats", "tmv_point_cache_stats", "tmv_set_batch_options", "tmv_batch_stats",
     "tmv_subgroup_stats", "tmv_validator_set_hashes",
     "tmv_verify_mixed_batch_ex", "tmv_verify_batch_device_ex", "tmv_verify_batches_device",
-    "tmv_verify_votes", "tmv_vote_sign_bytes_device", "tmv_merkle_roots",
+    "tmv_verify_votes", "tmv_vote_sign_bytes_device", "tmv_verify_votes_and_extensions",
+    "tmv_vote_extension_sign_bytes_device", "tmv_merkle_roots",
     "tmv_merkle_aunt_offsets", "tmv_merkle_proofs", "tmv_merkle_verify_proofs", "tmv_commit_hashes",
     "tmv_kernel_timing", "tmv_kernel_timing_read", "tmv_metrics_read", "tmv_metrics_reset",
     # include/tmhost.h
@@ -64,6 +67,7 @@ EXPORTS = [
     "tmv_header_hashes", "tmv_light_verify_many", "tmv_light_verify", "tmv_verify_vote_batch",
     "tmv_part_set_headers", "tmv_part_set_proofs", "tmv_parts_verify", "tmv_proofs_verify",
     "tmv_commit_hash_many", "tmv_blocks_validate_basic",
+    "tmv_vote_extension_sign_bytes", "tmv_vote_extension_template_encode", "tmv_verify_extended_votes",
 ]
 
 
@@ -102,6 +106,32 @@ def vote_templates(segments):
             ptrs.append((ctypes.cast(buf, ctypes.c_void_p), len(b)))
         arr[t] = VoteTemplate(ptrs[0][0], ptrs[0][1], ptrs[1][0], ptrs[1][1], ptrs[2][0], ptrs[2][1])
     return arr, keep
+
+
+class VoteExtTemplate(ctypes.Structure):
+    """tmv_vote_ext_template (include/tmverify.h): the tail the extensions of one (chain, height, round) share."""
+    _fields_ = [("tail", ctypes.c_void_p), ("tail_len", ctypes.c_uint32)]
+
+
+def vote_ext_templates(tails):
+    """[tail bytes] -> (ctypes array of VoteExtTemplate, keep-alive buffers)."""
+    keep = []
+    arr = (VoteExtTemplate * max(1, len(tails)))()
+    for t, b in enumerate(tails):
+        buf = ctypes.create_string_buffer(bytes(b), max(1, len(b)))
+        keep.append(buf)
+        arr[t] = VoteExtTemplate(ctypes.cast(buf, ctypes.c_void_p), len(b))
+    return arr, keep
+
+
+def _ext_args(ext_tmpl, ext_data, ext_off):
+    """The (template index, payload bytes, payload offsets) arrays of the extension entries, contiguous."""
+    ext_tmpl = np.ascontiguousarray(ext_tmpl, np.uint32)
+    ext_off = np.ascontiguousarray(ext_off, np.uint32)
+    ext_data = np.ascontiguousarray(ext_data, np.uint8)
+    if len(ext_off) != len(ext_tmpl) + 1:
+        raise ValueError("ext_off must hold one more entry than ext_tmpl")
+    return ext_tmpl, (ext_data if len(ext_data) else np.zeros(1, np.uint8)), ext_off
 
 
 class NativeError(RuntimeError):
@@ -179,6 +209,13 @@ def lib() -> ctypes.CDLL:
         L.tmv_vote_sign_bytes_device.restype = ctypes.c_int64
         L.tmv_vote_sign_bytes_device.argtypes = [vp, ctypes.POINTER(VoteTemplate), ctypes.c_uint32, vp,
                                                  ctypes.c_uint32, u8p, ctypes.c_size_t, u32p]
+        L.tmv_verify_votes_and_extensions.argtypes = [vp, ctypes.c_uint8, ctypes.c_uint32,
+                                                      ctypes.POINTER(VoteTemplate), ctypes.c_uint32, vp, ctypes.c_uint32,
+                                                      ctypes.POINTER(VoteExtTemplate), ctypes.c_uint32, u32p, u8p, u32p,
+                                                      ctypes.c_uint32, u8p, u8p, i8p]
+        L.tmv_vote_extension_sign_bytes_device.restype = ctypes.c_int64
+        L.tmv_vote_extension_sign_bytes_device.argtypes = [vp, ctypes.POINTER(VoteExtTemplate), ctypes.c_uint32, u32p,
+                                                           u8p, u32p, ctypes.c_uint32, u8p, ctypes.c_size_t, u32p]
         L.tmv_ed25519_verify_batch_device.argtypes = [vp, ctypes.c_int, vp, vp, vp, vp, ctypes.c_uint32, vp, vp]
         L.tmv_verify_mixed_batch_device.argtypes = [vp, ctypes.c_int, vp, vp, vp, vp, vp, ctypes.c_uint32, vp, vp]
         L.tmv_metrics_read.argtypes = [vp, ctypes.POINTER(Metrics)]
@@ -369,6 +406,43 @@ class Context:
         self._check(self._lib.tmv_vote_sign_bytes_device(self._h, arr, len(templates), vp, n, _p(msg), len(msg),
                                                          _p(off, ctypes.c_uint32)), "tmv_vote_sign_bytes_device")
         del keep
+        return msg[:total].tobytes(), off
+
+    def verify_votes_and_extensions(self, key_kind: int, flags: int, templates, votes, ext_tails, ext_tmpl, ext_data,
+                                    ext_off, pk, sig):
+        """tmv_verify_votes_and_extensions: the vote entries of verify_votes, then one extension entry per
+        ext_tmpl[j] (index into ext_tails) with the payload ext_data[ext_off[j]:ext_off[j+1]]; pk / sig hold the
+        vote entries' keys and signatures, then the extension entries'."""
+        votes = np.ascontiguousarray(votes, VOTE_DTYPE)
+        ext_tmpl, ext_data, ext_off = _ext_args(ext_tmpl, ext_data, ext_off)
+        nv, ne = len(votes), len(ext_tmpl)
+        arr, keep = vote_templates(templates)
+        earr, ekeep = vote_ext_templates(ext_tails)
+        out = np.zeros(max(nv + ne, 1), np.int8)
+        pk = pk if len(pk) else np.zeros(1, np.uint8)
+        sig = sig if len(sig) else np.zeros(1, np.uint8)
+        rc = self._check(self._lib.tmv_verify_votes_and_extensions(
+            self._h, key_kind, flags, arr, len(templates), votes.ctypes.data if nv else None, nv, earr,
+            len(ext_tails), _p(ext_tmpl, ctypes.c_uint32), _p(ext_data), _p(ext_off, ctypes.c_uint32), ne, _p(pk),
+            _p(sig), _p(out, ctypes.c_int8)), "tmv_verify_votes_and_extensions")
+        del keep, ekeep
+        return rc == TMV_ALL_VALID, out[:nv + ne]
+
+    def vote_extension_sign_bytes_device(self, ext_tails, ext_tmpl, ext_data, ext_off):
+        """The messages k_vote_ext_signbytes writes for the extension entries: (msg bytes, offsets)."""
+        ext_tmpl, ext_data, ext_off = _ext_args(ext_tmpl, ext_data, ext_off)
+        n = len(ext_tmpl)
+        earr, ekeep = vote_ext_templates(ext_tails)
+        off = np.zeros(n + 1, np.uint32)
+        args = (self._h, earr, len(ext_tails), _p(ext_tmpl, ctypes.c_uint32), _p(ext_data),
+                _p(ext_off, ctypes.c_uint32), n)
+        total = self._check(self._lib.tmv_vote_extension_sign_bytes_device(*args, None, 0, _p(off, ctypes.c_uint32)),
+                            "tmv_vote_extension_sign_bytes_device")
+        msg = np.zeros(max(total, 1), np.uint8)
+        self._check(self._lib.tmv_vote_extension_sign_bytes_device(*args, _p(msg), len(msg),
+                                                                   _p(off, ctypes.c_uint32)),
+                    "tmv_vote_extension_sign_bytes_device")
+        del ekeep
         return msg[:total].tobytes(), off
 
     def verify_mixed_batch_ex(self, flags: int, kind, pk, sig, msg, off):

@@ -40,6 +40,7 @@
 #include "ktimer.h"
 #include "verify_kernels.h"
 #include "votes.h"
+#include "vote_ext.h"
 #include "valset.h"
 #include "secp256k1.h"
 #include "secp256k1_launch.h"
@@ -1458,6 +1459,7 @@ int tmv_kernel_timing_read(tmv_ctx *ctx, const char *kernel, double *total_ms, u
   else if (!strcmp(kernel, "k_merkle_verify_proofs")) k = tmv::ktimer::kMerkleVerify;
   else if (!strcmp(kernel, "k_merkle_leaves")) k = tmv::ktimer::kMerkleLeaves;
   else if (!strcmp(kernel, "k_commit_leaves")) k = tmv::ktimer::kCommitLeaves;
+  else if (!strcmp(kernel, "k_vote_ext_signbytes")) k = tmv::ktimer::kVoteExtSignbytes;
   else { set_error("unknown timed kernel"); return TMV_ERR_ARG; }
   *total_ms = 0;
   *launches = 0;
@@ -1635,10 +1637,15 @@ enum class Scheme { Ed25519, Sr25519, Mixed, Ed25519Cached, Sr25519Cached };
 // Messages built on the device from vote templates (tmv_verify_votes):
 // the host sends the votes and the template table + blob; msg_off still
 // holds the host-computed offsets of the messages the device will write.
+#define TMV_VOTE_EXT_PART 1
+#include "vote_ext_runtime.h"
+#undef TMV_VOTE_EXT_PART
+
 struct VoteSrc {
   const tmv_vote *votes;
   const uint8_t *tab;  // n_tmpl VoteTab, then the template bytes
   size_t tab_bytes, blob_at;
+  const VoteExtSrc *ext = nullptr;  // extension entries after the votes (vote_ext_runtime.h)
 };
 
 // Stage one contiguous shard [lo, hi) to device d and launch; does not sync.
@@ -1851,8 +1858,10 @@ static int stage_and_launch(tmv_ctx *ctx, uint32_t flags, Device &d, HostLane &l
   const uint32_t G = merged ? o.p.groups : 0;
   const size_t kind_at = L.total;
   const size_t votes_at = L.total + (sch == Scheme::Mixed ? align16(n) : 0) + (cached ? align16(4ull * n) : 0);
-  const size_t tab_at = votes_at + (vs ? align16(sizeof(tmv_vote) * n) : 0);
-  const size_t runs_at = tab_at + (vs ? align16(vs->tab_bytes) : 0);
+  const VoteExtStage xp = vote_ext_plan(vs ? vs->ext : nullptr, lo, hi, 0);  // vote / extension entries of the chunk
+  const size_t tab_at = votes_at + (vs ? align16(sizeof(tmv_vote) * xp.nv) : 0);
+  const VoteExtStage xe = vote_ext_plan(vs ? vs->ext : nullptr, lo, hi, tab_at + (vs ? align16(vs->tab_bytes) : 0));
+  const size_t runs_at = xe.end;
   const size_t run_cap = (size_t)distinct + G;  // key segments cut at group edges
   const size_t order_at = runs_at + align16(4ull * (2 * run_cap + 1 + G + 1));
   const size_t total = merged ? order_at + align16(4ull * n) : runs_at;
@@ -1867,8 +1876,9 @@ static int stage_and_launch(tmv_ctx *ctx, uint32_t flags, Device &d, HostLane &l
   par_memcpy(h + L.sig, sig + 64ull * lo, 64ull * n);
   for (uint32_t i = 0; i <= n; i++) off[i] = msg_off[lo + i] - base;
   if (vs) {
-    par_memcpy(h + votes_at, vs->votes + lo, sizeof(tmv_vote) * n);
+    if (xe.nv) par_memcpy(h + votes_at, vs->votes + lo, sizeof(tmv_vote) * xe.nv);
     std::memcpy(h + tab_at, vs->tab, vs->tab_bytes);
+    if (vs->ext) vote_ext_stage(*vs->ext, xe, h);
   } else if (mbytes) {
     par_memcpy(h + L.msg, msg + base, mbytes);
   }
@@ -1937,8 +1947,12 @@ static int stage_and_launch(tmv_ctx *ctx, uint32_t flags, Device &d, HostLane &l
     ctx->m_h2d += L.msg + (total - L.total);
     const tmv::VoteTab *tab = reinterpret_cast<const tmv::VoteTab *>(dd + tab_at);
     if ((e = tmv::launch_vote_signbytes(reinterpret_cast<const tmv_vote *>(dd + votes_at), tab,
-                                        dd + tab_at + vs->blob_at, doff, n, dd + L.msg, ln.stream)) != hipSuccess) {
+                                        dd + tab_at + vs->blob_at, doff, xe.nv, dd + L.msg, ln.stream)) != hipSuccess) {
       set_error("k_vote_signbytes", e);
+      return TMV_ERR_LAUNCH;
+    }
+    if (vs->ext && (e = vote_ext_launch(*vs->ext, xe, dd, doff, dd + L.msg, ln.stream)) != hipSuccess) {
+      set_error("k_vote_ext_signbytes", e);
       return TMV_ERR_LAUNCH;
     }
   } else if ((e = hipMemcpyAsync(ln.d_in.ptr, h, total, hipMemcpyHostToDevice, ln.stream)) != hipSuccess) {
@@ -2753,6 +2767,11 @@ int tmv_ed25519_verify_batch_device(tmv_ctx *ctx, int device, const uint8_t *d_p
 
 }  // extern "C"
 
+
+// tmv_verify_votes_and_extensions, tmv_vote_extension_sign_bytes_device
+#define TMV_VOTE_EXT_PART 2
+#include "vote_ext_runtime.h"
+#undef TMV_VOTE_EXT_PART
 
 // tmv_merkle_proofs, tmv_merkle_verify_proofs, tmv_merkle_aunt_offsets
 #include "merkle_runtime.h"

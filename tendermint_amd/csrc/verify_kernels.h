@@ -234,6 +234,11 @@ hipError_t launch_key_merged_check(bool sr, const uint8_t *pk, const uint8_t *si
 struct VoteTab;
 hipError_t launch_vote_signbytes(const tmv_vote *votes, const VoteTab *tab, const uint8_t *blob,
                                  const uint32_t *off, uint32_t n, uint8_t *msg, hipStream_t stream);
+// Vote-extension sign-bytes (signbytes_kernels.hip, vote_ext.h).
+struct VoteExtTab;
+hipError_t launch_vote_ext_signbytes(const VoteExtTab *tab, const uint8_t *blob, const uint32_t *tmpl,
+                                     const uint32_t *src_off, const uint8_t *data, const uint32_t *off, uint32_t n,
+                                     uint8_t *msg, uint32_t wave_min, hipStream_t stream);
 
 hipError_t launch_ed25519_verify(const uint8_t *pk, const uint8_t *sig, const uint8_t *msg,
                                  const uint32_t *msg_off, uint32_t n, const ge_precomp *btable,

@@ -694,6 +694,8 @@ class Vote:
     validator_address: bytes
     validator_index: int
     signature: bytes = b""
+    extension: bytes = b""
+    extension_signature: bytes = b""
 
 
 def verify_vote_batch_call(fn, ctx_handle, chain_id: str, votes: List[Vote], keys: List[Tuple[int, bytes]]
@@ -726,6 +728,109 @@ def verify_vote_batch(ctx, chain_id: str, votes: List[Vote], keys: List[Tuple[in
                                             ctypes.c_uint32, ctypes.POINTER(ctypes.c_int32)]
         L._tmhost_votes = True
     return verify_vote_batch_call(L.tmv_verify_vote_batch, ctx.handle, chain_id, votes, keys)
+
+
+# ---------------------------------------------------------------- vote extensions
+VOTE_MODE_VERIFY, VOTE_MODE_VERIFY_AND_EXTENSION, VOTE_MODE_EXTENSION = 0, 1, 2
+
+
+class CExtVoteIn(ctypes.Structure):
+    """tmv_ext_vote_in (include/tmhost.h)."""
+    _fields_ = [("vote", CVoteIn), ("extension", _u8p), ("extension_len", ctypes.c_uint32),
+                ("extension_signature", _u8p), ("extension_signature_len", ctypes.c_uint32)]
+
+
+def _setup_vote_ext(L):
+    if not getattr(L, "_tmhost_vote_ext", False):
+        L.tmv_vote_extension_sign_bytes.restype = ctypes.c_size_t
+        L.tmv_vote_extension_sign_bytes.argtypes = [ctypes.c_char_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_char_p,
+                                                    ctypes.c_size_t, _u8p, ctypes.c_size_t]
+        L.tmv_vote_extension_template_encode.restype = ctypes.c_size_t
+        L.tmv_vote_extension_template_encode.argtypes = [ctypes.c_char_p, ctypes.c_int64, ctypes.c_int32, _u8p,
+                                                         ctypes.c_size_t]
+        L.tmv_verify_extended_votes.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p,
+                                                ctypes.POINTER(CExtVoteIn), ctypes.c_uint32,
+                                                ctypes.POINTER(ctypes.c_int32), _u8p]
+        L._tmhost_vote_ext = True
+    return L
+
+
+def vote_extension_sign_bytes(chain_id: str, height: int, round_: int, extension: bytes, lib=None) -> bytes:
+    """types.VoteExtensionSignBytes through the C++ encoder (tmv_vote_extension_sign_bytes)."""
+    L = _setup_vote_ext(lib or _native.lib())
+    cap = len(extension) + len(chain_id.encode()) + 64
+    out = (ctypes.c_uint8 * cap)()
+    n = L.tmv_vote_extension_sign_bytes(chain_id.encode(), height, round_, extension, len(extension),
+                                        ctypes.cast(out, _u8p), cap)
+    return bytes(out[:n])
+
+
+def vote_extension_template(chain_id: str, height: int, round_: int, lib=None) -> bytes:
+    """The tail the extension messages of one (chain_id, height, round) share
+    (tmv_vote_extension_template_encode)."""
+    L = _setup_vote_ext(lib or _native.lib())
+    cap = len(chain_id.encode()) + 32
+    out = (ctypes.c_uint8 * cap)()
+    n = L.tmv_vote_extension_template_encode(chain_id.encode(), height, round_, ctypes.cast(out, _u8p), cap)
+    return bytes(out[:n])
+
+
+def verify_extended_votes_call(fn, ctx_handle, mode: int, chain_id: str, votes: List[Vote],
+                               keys: List[Tuple[int, bytes]]) -> List[Tuple[int, int]]:
+    """votes[i] checked against keys[i] = (key kind, public key) as `mode` says
+    (VOTE_MODE_*); fn = tmv_verify_extended_votes (or the CPU harness's twin).
+    Returns (TMV_VOTE_*, failed signature: 0 none, 1 vote, 2 extension) per vote."""
+    k = _Keep()
+    n = len(votes)
+    arr = (CExtVoteIn * max(1, n))()
+    for i, (v, (kind, pk)) in enumerate(zip(votes, keys)):
+        bid = None
+        if v.block_id is not None and (v.block_id.hash or v.block_id.psh_total or v.block_id.psh_hash):
+            b = _c_block_id(k, v.block_id)
+            k.refs.append(b)
+            bid = ctypes.pointer(b)
+        a, al = k.buf(v.validator_address)
+        s, sl = k.buf(v.signature)
+        p, pl = k.buf(pk)
+        e, el = k.buf(v.extension)
+        es, esl = k.buf(v.extension_signature)
+        arr[i] = CExtVoteIn(CVoteIn(v.type, v.height, v.round, bid, v.timestamp[0], v.timestamp[1], a, al, s, sl, kind,
+                                    p, pl), e, el, es, esl)
+    res = (ctypes.c_int32 * max(1, n))()
+    failed = (ctypes.c_uint8 * max(1, n))()
+    rc = fn(ctx_handle, mode, chain_id.encode(), arr, n, res, failed)
+    if rc < 0:
+        raise NativeError(f"tmv_verify_extended_votes failed ({rc}): {_native.last_error()}")
+    return [(res[i], failed[i]) for i in range(n)]
+
+
+def verify_extended_votes(ctx, mode: int, chain_id: str, votes: List[Vote], keys: List[Tuple[int, bytes]]
+                          ) -> List[Tuple[int, int]]:
+    """Vote.Verify / VerifyVoteAndExtension / VerifyExtension (types/vote.go:226-276)
+    of many votes, their vote and extension signatures in one engine call per key kind."""
+    L = _setup_vote_ext(_native.lib())
+    return verify_extended_votes_call(L.tmv_verify_extended_votes, ctx.handle, mode, chain_id, votes, keys)
+
+
+@dataclass
+class ExtendedCommitSig:
+    """types.ExtendedCommitSig (types/block.go:722-727): a CommitSig with the
+    vote extension and its signature."""
+    block_id_flag: int = BLOCK_ID_FLAG_ABSENT
+    validator_address: bytes = b""
+    timestamp: Tuple[int, int] = ZERO_TIME
+    signature: bytes = b""
+    extension: bytes = b""
+    extension_signature: bytes = b""
+
+
+@dataclass
+class ExtendedCommit:
+    """types.ExtendedCommit (types/block.go:1003-1011)."""
+    height: int
+    round: int
+    block_id: BlockID
+    extended_signatures: List[ExtendedCommitSig] = field(default_factory=list)
 
 
 # ---------------------------------------------------------------- block part sets and merkle proofs

@@ -127,3 +127,29 @@ def vote_sign_bytes(chain_id: str, vtype: int, height: int, round_: int, block_i
     """types.VoteSignBytes: MarshalDelimited(CanonicalizeVote(chainID, vote))."""
     body = canonical_vote(chain_id, vtype, height, round_, block_id, timestamp)
     return uvarint(len(body)) + body
+
+
+def canonical_vote_extension(chain_id: str, height: int, round_: int, extension: bytes) -> bytes:
+    """Proto encoding of CanonicalVoteExtension (types/canonical.go:68-78,
+    proto/tendermint/types/canonical.pb.go:657-689): extension, height and
+    round as sfixed64, chain_id; zero / empty fields omitted."""
+    out = b""
+    if extension:
+        out += b"\x0a" + uvarint(len(extension)) + extension
+    if height != 0:
+        out += b"\x11" + struct.pack("<q", height)
+    if round_ != 0:
+        out += b"\x19" + struct.pack("<q", round_)
+    cid = chain_id.encode()
+    if cid:
+        out += b"\x22" + uvarint(len(cid)) + cid
+    return out
+
+
+def vote_extension_sign_bytes(chain_id: str, height: int, round_: int, extension: bytes) -> bytes:
+    """types.VoteExtensionSignBytes (types/vote.go:159-172):
+    MarshalDelimited(CanonicalizeVoteExtension(chainID, vote)).  The reference
+    holds no known-answer vector for these bytes; they are pinned by the
+    marshal code alone."""
+    body = canonical_vote_extension(chain_id, height, round_, extension)
+    return uvarint(len(body)) + body

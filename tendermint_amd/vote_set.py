@@ -12,11 +12,27 @@ VoteSet (types/vote_set.go) with its signature checks moved into batches.
                                 voting power, verified together, then later
                                 votes are verified as they arrive
 
+  * VoteSet(..., extensions_enabled=True)
+                             == NewExtendedVoteSet (types/vote_set.go:95-103):
+                                every vote goes through VerifyVoteAndExtension
+                                (types/vote.go:245-262), so a non-nil precommit
+                                carries TWO signatures of its validator, the
+                                second over VoteExtensionSignBytes; both go
+                                into the same engine call
+                                (tmv_verify_extended_votes)
+  * extended_commits_to_vote_sets(jobs)
+                             == ExtendedCommit.ToExtendedVoteSet
+                                (types/block.go:1037-1071) under
+                                votesFromExtendedCommit
+                                (internal/consensus/state.go:722-732) for many
+                                extended commits, the 2n signatures of all of
+                                them in one engine call
+
 Bookkeeping (votes by validator, votes by block, the first 2/3 majority,
 conflicting votes) follows vote_set.go:247-314 (addVerifiedVote) and
 :685-692 (blockVotes).  Error texts are the reference's.  Peer 2/3 claims
-(SetPeerMaj23), vote extensions and MakeCommit are out of scope: they touch
-no signature.
+(SetPeerMaj23), MakeCommit / MakeExtendedCommit and the ABCI
+VerifyVoteExtension call into the application are out of scope.
 """
 from __future__ import annotations
 
@@ -45,10 +61,10 @@ def _canonical_time(ts: Tuple[int, int]) -> str:
 
 
 def vote_string(v: Vote) -> str:
-    """Vote.String() (types/vote.go:191-224) of an extension-free vote."""
+    """Vote.String() (types/vote.go:191-224)."""
     bh = _fp(v.block_id.hash) if v.block_id.hash else "nil"
     return "Vote{%d:%s %d/%d %s %s %s %d @ %s}" % (v.validator_index, _fp(v.validator_address), v.height, v.round,
-                                                  _TYPE_NAME.get(v.type, "?"), bh, _fp(v.signature), 0,
+                                                  _TYPE_NAME.get(v.type, "?"), bh, _fp(v.signature), len(v.extension),
                                                   _canonical_time(v.timestamp))
 
 
@@ -57,7 +73,8 @@ def _block_key(b: H.BlockID):
 
 
 def _pubkey_string(kind: int, pk: bytes) -> str:
-    return ("PubKeyEd25519{%s}" if kind == H.TMV_KIND_ED25519 else "PubKeySr25519{%s}") % _hexu(pk)
+    name = {H.TMV_KIND_ED25519: "PubKeyEd25519{%s}", H.TMV_KIND_SECP256K1: "PubKeySecp256k1{%s}"}
+    return name.get(kind, "PubKeySr25519{%s}") % _hexu(pk)
 
 
 VerifyFn = Callable[[str, List[Vote], List[Tuple[int, bytes]]], List[int]]
@@ -69,9 +86,19 @@ class VoteSet:
     per vote; e.g. lambda c, v, k: host.verify_vote_batch(ctx, c, v, k))."""
 
     def __init__(self, chain_id: str, height: int, round_: int, msg_type: int, vals: H.ValidatorSet,
-                 verify: VerifyFn):
+                 verify: Optional[VerifyFn], extensions_enabled: bool = False,
+                 verify_extended: Optional[VerifyFn] = None):
+        """extensions_enabled: NewExtendedVoteSet; the signatures are then
+        checked by `verify_extended` (same arguments and results as `verify`,
+        with VerifyVoteAndExtension's meaning; e.g. lambda c, v, k: [r for r, _
+        in host.verify_extended_votes(ctx, host.VOTE_MODE_VERIFY_AND_EXTENSION,
+        c, v, k)]) and `verify` is not used."""
         self.chain_id, self.height, self.round, self.type, self.vals = chain_id, height, round_, msg_type, vals
         self.verify = verify
+        self.extensions_enabled = extensions_enabled
+        self.verify_extended = verify_extended
+        if extensions_enabled and verify_extended is None:
+            raise ValueError("an extended vote set needs verify_extended")
         n = len(vals.validators)
         self.votes: List[Optional[Vote]] = [None] * n
         self.sum = 0
@@ -107,7 +134,8 @@ class VoteSet:
         if cand:
             keys = [(self.vals.validators[votes[i].validator_index].key_kind,
                      self.vals.validators[votes[i].validator_index].pub_key) for i in cand]
-            res = self.verify(self.chain_id, [votes[i] for i in cand], keys)
+            check = self.verify_extended if self.extensions_enabled else self.verify
+            res = check(self.chain_id, [votes[i] for i in cand], keys)
             self.signature_batches += 1
             sig_res = dict(zip(cand, res))
         out = []
@@ -166,6 +194,8 @@ class VoteSet:
             why = "invalid validator address" if sig == H.VOTE_ERR_INVALID_ADDRESS else "invalid signature"
             return False, "failed to verify vote with ChainID %s and PubKey %s: %s" % (
                 self.chain_id, _pubkey_string(val.key_kind, val.pub_key), why)
+        if not self.extensions_enabled and (vote.extension_signature or vote.extension):  # vote_set.go:218-220
+            return False, "unexpected vote extension data present in vote"
         added, conflicting = self._add_verified(vote, key, self.vals.validators[vote.validator_index].voting_power)
         if conflicting is not None:
             return added, "conflicting votes from validator %s" % _hexu(conflicting.validator_address)
@@ -232,3 +262,187 @@ class VoteBuffer:
         votes, self.pending, self.pending_power = self.pending, [], 0
         self.flushed = True
         return list(zip(votes, self.vs.add_votes(votes)))
+
+
+# ---------------------------------------------------------------- vote extensions: restatements
+MAX_SIGNATURE_SIZE = 64                # types/vote.go: max(ed25519.SignatureSize, 64)
+MAX_VOTE_EXTENSION_SIZE = 1024 * 1024  # types/vote.go:20
+
+
+def _block_id_is_nil(b: H.BlockID) -> bool:
+    return not b.hash and b.psh_total == 0 and not b.psh_hash
+
+
+def _block_id_string(b: H.BlockID) -> str:  # BlockID.String (types/block.go:1416-1418)
+    return "%s:%d:%s" % (_hexu(b.hash), b.psh_total, _fp(b.psh_hash))
+
+
+def vote_validate_basic(v: Vote) -> Optional[str]:
+    """Vote.ValidateBasic (types/vote.go:281-345)."""
+    if v.type not in (H.PREVOTE_TYPE, H.PRECOMMIT_TYPE):
+        return "invalid Type"
+    if v.height < 0:
+        return "negative Height"
+    if v.round < 0:
+        return "negative Round"
+    b = v.block_id
+    if b.hash and len(b.hash) != 32:
+        return "wrong BlockID: wrong Hash: expected size to be 32 bytes, got %d bytes" % len(b.hash)
+    if b.psh_hash and len(b.psh_hash) != 32:
+        return ("wrong BlockID: wrong PartSetHeader: wrong Hash: expected size to be 32 bytes, got %d bytes" %
+                len(b.psh_hash))
+    nil = _block_id_is_nil(b)
+    if not nil and not (len(b.hash) == 32 and b.psh_total > 0 and len(b.psh_hash) == 32):
+        return "blockID must be either empty or complete, got: %s" % _block_id_string(b)
+    if len(v.validator_address) != 20:
+        return "expected ValidatorAddress size to be 20 bytes, got %d bytes" % len(v.validator_address)
+    if v.validator_index < 0:
+        return "negative ValidatorIndex"
+    if not v.signature:
+        return "signature is missing"
+    if len(v.signature) > MAX_SIGNATURE_SIZE:
+        return "signature is too big (max: %d)" % MAX_SIGNATURE_SIZE
+    if v.type != H.PRECOMMIT_TYPE or nil:
+        if v.extension:
+            return "unexpected vote extension"
+        if v.extension_signature:
+            return "unexpected vote extension signature"
+    else:
+        if len(v.extension_signature) > MAX_SIGNATURE_SIZE:
+            return "vote extension signature is too big (max: %d)" % MAX_SIGNATURE_SIZE
+        if not v.extension_signature and v.extension:
+            return "vote extension signature absent on vote with extension"
+    return None
+
+
+def _commit_sig_validate_basic(s) -> Optional[str]:
+    """CommitSig.ValidateBasic (types/block.go:657-694)."""
+    if s.block_id_flag not in (H.BLOCK_ID_FLAG_ABSENT, H.BLOCK_ID_FLAG_COMMIT, H.BLOCK_ID_FLAG_NIL):
+        return "unknown BlockIDFlag: %d" % s.block_id_flag
+    if s.block_id_flag == H.BLOCK_ID_FLAG_ABSENT:
+        if s.validator_address:
+            return "validator address is present"
+        if tuple(s.timestamp) != H.ZERO_TIME:
+            return "time is present"
+        if s.signature:
+            return "signature is present"
+        return None
+    if len(s.validator_address) != 20:
+        return "expected ValidatorAddress size to be 20 bytes, got %d bytes" % len(s.validator_address)
+    if not s.signature:
+        return "signature is missing"
+    if len(s.signature) > MAX_SIGNATURE_SIZE:
+        return "signature is too big (max: %d)" % MAX_SIGNATURE_SIZE
+    return None
+
+
+def extended_commit_sig_validate_basic(s: H.ExtendedCommitSig) -> Optional[str]:
+    """ExtendedCommitSig.ValidateBasic (types/block.go:751-770)."""
+    err = _commit_sig_validate_basic(s)
+    if err:
+        return err
+    if s.block_id_flag == H.BLOCK_ID_FLAG_COMMIT:
+        if len(s.extension) > MAX_VOTE_EXTENSION_SIZE:
+            return "vote extension is too big (max: %d)" % MAX_VOTE_EXTENSION_SIZE
+        if len(s.extension_signature) > MAX_SIGNATURE_SIZE:
+            return "vote extension signature is too big (max: %d)" % MAX_SIGNATURE_SIZE
+        return None
+    if not s.extension_signature and s.extension:
+        return "vote extension signature absent on vote with extension"
+    return None
+
+
+def extended_commit_sig_ensure_extension(s: H.ExtendedCommitSig) -> Optional[str]:
+    """ExtendedCommitSig.EnsureExtension (types/block.go:774-779)."""
+    if s.block_id_flag == H.BLOCK_ID_FLAG_COMMIT and not s.extension_signature:
+        return "vote extension data is missing"
+    return None
+
+
+def extended_commit_validate_basic(ec: H.ExtendedCommit) -> Optional[str]:
+    """ExtendedCommit.ValidateBasic (types/block.go:1206-1229)."""
+    if ec.height < 0:
+        return "negative Height"
+    if ec.round < 0:
+        return "negative Round"
+    if ec.height >= 1:
+        if _block_id_is_nil(ec.block_id):
+            return "commit cannot be for nil block"
+        if not ec.extended_signatures:
+            return "no signatures in commit"
+        for i, s in enumerate(ec.extended_signatures):
+            err = extended_commit_sig_validate_basic(s)
+            if err:
+                return "wrong ExtendedCommitSig #%d: %s" % (i, err)
+    return None
+
+
+def extended_commit_ensure_extensions(ec: H.ExtendedCommit) -> Optional[str]:
+    """ExtendedCommit.EnsureExtensions (types/block.go:1096-1103)."""
+    for s in ec.extended_signatures:
+        err = extended_commit_sig_ensure_extension(s)
+        if err:
+            return err
+    return None
+
+
+def get_extended_vote(ec: H.ExtendedCommit, idx: int) -> Vote:
+    """ExtendedCommit.GetExtendedVote (types/block.go:1138-1152)."""
+    s = ec.extended_signatures[idx]
+    bid = ec.block_id if s.block_id_flag == H.BLOCK_ID_FLAG_COMMIT else H.BlockID()
+    return Vote(H.PRECOMMIT_TYPE, ec.height, ec.round, bid, tuple(s.timestamp), s.validator_address, idx, s.signature,
+                s.extension, s.extension_signature)
+
+
+def extended_commits_to_vote_sets(jobs, verify_extended: VerifyFn):
+    """ExtendedCommit.ToExtendedVoteSet (types/block.go:1037-1071) as
+    votesFromExtendedCommit runs it (internal/consensus/state.go:722-732), for
+    many jobs = (chain_id, validator set, extended commit) at once: what a
+    node does with its stored extended commit when it starts or leaves
+    blocksync.  The vote and extension signatures of ALL jobs are verified in
+    one `verify_extended` call (one per chain_id, if the jobs name several);
+    each job is then walked in the reference's order and yields its VoteSet,
+    or the text of the panic / error the reference would have ended with."""
+    plans = []
+    by_chain: Dict[str, list] = {}
+    for j, (chain_id, vals, ec) in enumerate(jobs):
+        if ec.height == 0:  # NewVoteSet (types/vote_set.go:77-79)
+            plans.append((None, [], "Cannot make VoteSet for height == 0, doesn't make sense."))
+            continue
+        vs = VoteSet(chain_id, ec.height, ec.round, H.PRECOMMIT_TYPE, vals, None, True, verify_extended)
+        steps = []  # (vote, validate-basic error, pre-signature result, index among the chain's candidates)
+        for idx, s in enumerate(ec.extended_signatures):
+            if s.block_id_flag == H.BLOCK_ID_FLAG_ABSENT:
+                continue
+            v = get_extended_vote(ec, idx)
+            bad = vote_validate_basic(v)
+            if bad is not None:
+                steps.append((v, bad, None, -1))
+                break  # the reference panics here
+            pre = vs._precheck(v)
+            at = -1
+            if pre is None:
+                val = vals.validators[v.validator_index]
+                c = by_chain.setdefault(chain_id, [[], []])
+                at = len(c[0])
+                c[0].append(v)
+                c[1].append((val.key_kind, val.pub_key))
+            steps.append((v, None, pre, at))
+        plans.append((vs, steps, None))
+    results = {c: verify_extended(c, vk[0], vk[1]) for c, vk in by_chain.items()}
+    out = []
+    for (chain_id, _, _), (vs, steps, text) in zip(jobs, plans):
+        if text is None:
+            for v, bad, pre, at in steps:
+                if bad is not None:
+                    text = "failed to validate vote reconstructed from LastCommit: " + bad
+                    break
+                added, err = pre if pre is not None else vs._add_checked(v, results[chain_id][at])
+                if not added or err is not None:
+                    text = "failed to reconstruct vote set from extended commit: " + (
+                        err if err is not None else "%!w(<nil>)")
+                    break
+            if text is None and not vs.has_two_thirds_majority():
+                text = "extended commit does not have +2/3 majority"
+        out.append(text if text is not None else vs)
+    return out
