@@ -111,6 +111,26 @@ int tmv_ed25519_verify(tmv_ctx *ctx, const uint8_t *pk, const uint8_t *msg, size
 int tmv_secp256k1_verify_batch(tmv_ctx *ctx, const uint8_t *pk, const uint8_t *sig, const uint8_t *msg,
                                const uint32_t *msg_off, uint32_t n, uint8_t *valid_out);
 
+/* tmv_secp256k1_verify_batch with options.  flags: 0 (the call above) or
+ *   TMV_FLAG_KEY_CACHE  keep the keys' comb tables on the device: an LRU of
+ *   TMV_SECP_KEY_CACHE_CAPACITY keys (default 4,096; 0 = off) on the
+ *   context's first device, apart from the ed25519/sr25519 cache.  A cached
+ *   key is the 960 affine multiples d 16^j Q (j < 64, 1 <= d <= 15), 61,440
+ *   bytes, so u1 G + u2 Q is 128 additions and no doublings; the table (240
+ *   MiB at the default) is allocated at the first cached call, and the first
+ *   call that sees a key pays its build.  A call with more distinct keys than
+ *   the cache holds, or made when the table found no room, takes the uncached
+ *   path transparently.  A key that does not parse takes no slot.
+ * Verdicts are identical with and without the flag for every input; the
+ * argument rules are those of tmv_secp256k1_verify_batch, and any other flag
+ * bit is TMV_ERR_ARG.  No reference counterpart (btcec parses the key per
+ * call). */
+int tmv_secp256k1_verify_batch_ex(tmv_ctx *ctx, uint32_t flags, const uint8_t *pk, const uint8_t *sig,
+                                  const uint8_t *msg, const uint32_t *msg_off, uint32_t n, uint8_t *valid_out);
+/* Counters of that cache since tmv_open, per distinct key per call: hits
+ * (found), misses (built); used / capacity in keys.  Any pointer may be NULL. */
+int tmv_secp256k1_key_cache_stats(tmv_ctx *ctx, uint64_t *hits, uint64_t *misses, uint32_t *used, uint32_t *capacity);
+
 /* Single secp256k1 verification (secp256k1.go:206-226).  Returns 0 without
  * touching the device when pk_len != 33 or sig_len != 64 (the reference
  * returns false for a signature of another size; keys of another size cannot
@@ -293,7 +313,8 @@ int tmv_verify_mixed_batch_ex(tmv_ctx *ctx, uint32_t flags, const uint8_t *kind,
 /* Live kernel timing (profiling aid; bench.py's roofline object).  enable != 0:
  * every later launch of the timed kernels -- "k_msm_accum" (batch-equation
  * bucket sums), "k_msm_wpart" (window running sums), "k_prep_fused" (decode +
- * challenge), "k_secp_prep" and "k_secp_verify" (secp256k1), "k_merkle_leaves_long",
+ * challenge), "k_secp_prep" and "k_secp_verify" (secp256k1), "k_secp_key_table", "k_secp_prep_cached" and
+ * "k_secp_verify_comb" (secp256k1 with TMV_FLAG_KEY_CACHE), "k_merkle_leaves_long",
  * "k_merkle_leaves", "k_merkle_tree_levels", "k_merkle_aunts" and "k_merkle_verify_proofs" (the launches
  * of tmv_merkle_proofs / tmv_merkle_verify_proofs), "k_commit_leaves" (tmv_commit_hashes) -- is bracketed by HIP timing events on the stream it runs on
  * (process-wide, two event records per launch); 0 turns it off.

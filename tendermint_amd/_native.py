@@ -52,7 +52,8 @@ VOTE_DTYPE = np.dtype([("ts_seconds", "<i8"), ("ts_nanos", "<i4"), ("tmpl", "<u4
 EXPORTS = [
     "tmv_open", "tmv_open_logical", "tmv_close", "tmv_num_devices", "tmv_last_error", "tmv_version",
     "tmv_ed25519_verify_batch", "tmv_ed25519_verify", "tmv_sr25519_verify_batch",
-    "tmv_secp256k1_verify_batch", "tmv_secp256k1_verify",
+    "tmv_secp256k1_verify_batch", "tmv_secp256k1_verify", "tmv_secp256k1_verify_batch_ex",
+    "tmv_secp256k1_key_cache_stats",
     "tmv_verify_mixed_batch", "tmv_ed25519_verify_batch_device", "tmv_verify_mixed_batch_device",
     "tmv_verify_batch_ex", "tmv_key_cache_stats", "tmv_point_cache_stats", "tmv_set_batch_options", "tmv_batch_stats",
     "tmv_subgroup_stats", "tmv_validator_set_hashes",
@@ -174,6 +175,10 @@ def lib() -> ctypes.CDLL:
         L.tmv_ed25519_verify.argtypes = [vp, u8p, u8p, ctypes.c_size_t, u8p, ctypes.c_size_t]
         L.tmv_secp256k1_verify_batch.argtypes = [vp, u8p, u8p, u8p, u32p, ctypes.c_uint32, u8p]
         L.tmv_secp256k1_verify.argtypes = [vp, u8p, ctypes.c_size_t, u8p, ctypes.c_size_t, u8p, ctypes.c_size_t]
+        L.tmv_secp256k1_verify_batch_ex.argtypes = [vp, ctypes.c_uint32, u8p, u8p, u8p, u32p, ctypes.c_uint32, u8p]
+        L.tmv_secp256k1_key_cache_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64),
+                                                    ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32),
+                                                    ctypes.POINTER(ctypes.c_uint32)]
         L.tmv_sr25519_verify_batch.argtypes = [vp, u8p, u8p, u8p, u32p, ctypes.c_uint32, i8p]
         L.tmv_verify_mixed_batch.argtypes = [vp, u8p, u8p, u8p, u8p, u32p, ctypes.c_uint32, i8p]
         L.tmv_verify_batch_ex.argtypes = [vp, ctypes.c_uint8, ctypes.c_uint32, u8p, u8p, u8p, u32p, ctypes.c_uint32,
@@ -335,6 +340,28 @@ class Context:
                                                               _p(off, ctypes.c_uint32), n, _p(out)),
                          "tmv_secp256k1_verify_batch")
         return rc == TMV_ALL_VALID, out[:n]
+
+    def secp256k1_verify_batch_ex(self, pk: np.ndarray, sig: np.ndarray, msg: np.ndarray, off: np.ndarray,
+                                  flags: int = TMV_FLAG_KEY_CACHE):
+        """secp256k1_verify_batch with flags: TMV_FLAG_KEY_CACHE verifies against the keys' comb tables kept on
+        the device (TMV_SECP_KEY_CACHE_CAPACITY keys); the verdicts are the same."""
+        n = len(off) - 1
+        out = np.zeros(max(n, 1), np.uint8)
+        msg = msg if len(msg) else np.zeros(1, np.uint8)
+        pk = pk if len(pk) else np.zeros(1, np.uint8)
+        sig = sig if len(sig) else np.zeros(1, np.uint8)
+        rc = self._check(self._lib.tmv_secp256k1_verify_batch_ex(self._h, flags, _p(pk), _p(sig), _p(msg),
+                                                                 _p(off, ctypes.c_uint32), n, _p(out)),
+                         "tmv_secp256k1_verify_batch_ex")
+        return rc == TMV_ALL_VALID, out[:n]
+
+    def secp256k1_key_cache_stats(self):
+        h, m = ctypes.c_uint64(), ctypes.c_uint64()
+        u, c = ctypes.c_uint32(), ctypes.c_uint32()
+        self._check(self._lib.tmv_secp256k1_key_cache_stats(self._h, ctypes.byref(h), ctypes.byref(m),
+                                                            ctypes.byref(u), ctypes.byref(c)),
+                    "tmv_secp256k1_key_cache_stats")
+        return {"hits": h.value, "misses": m.value, "used": u.value, "capacity": c.value}
 
     def secp256k1_verify(self, pk: bytes, msg: bytes, sig: bytes) -> bool:
         a = np.frombuffer(pk + b"\0", np.uint8).copy()

@@ -33,6 +33,9 @@
 extern "C" int tmv_secp256k1_verify_batch(tmv_ctx *ctx, const uint8_t *pk, const uint8_t *sig, const uint8_t *msg,
                                           const uint32_t *msg_off, uint32_t n, uint8_t *valid_out)
     __attribute__((weak));
+extern "C" int tmv_secp256k1_verify_batch_ex(tmv_ctx *ctx, uint32_t flags, const uint8_t *pk, const uint8_t *sig,
+                                             const uint8_t *msg, const uint32_t *msg_off, uint32_t n,
+                                             uint8_t *valid_out) __attribute__((weak));
 
 namespace tmh_internal {
 
@@ -517,7 +520,11 @@ struct GpuBackend {
       pb.off.push_back((uint32_t)pb.msg.size());
     }
     if (pb.msg.empty()) pb.msg.push_back(0);
-    if (tmv_secp256k1_verify_batch) {  // the device entry (libtmgpu.so: always)
+    if (tmv_secp256k1_verify_batch_ex) {  // the device entry (libtmgpu.so: always), validators' keys cached
+      const int rc = tmv_secp256k1_verify_batch_ex(ctx, TMV_FLAG_KEY_CACHE, pk.data(), pb.sig.data(), pb.msg.data(),
+                                                   pb.off.data(), (uint32_t)m, valid.data());
+      if (rc < 0) { infra = rc; return; }
+    } else if (tmv_secp256k1_verify_batch) {
       const int rc = tmv_secp256k1_verify_batch(ctx, pk.data(), pb.sig.data(), pb.msg.data(), pb.off.data(),
                                                 (uint32_t)m, valid.data());
       if (rc < 0) { infra = rc; return; }

@@ -34,6 +34,9 @@ extern "C" int tmv_verify_votes_and_extensions(tmv_ctx *ctx, uint8_t key_kind, u
 extern "C" int tmv_secp256k1_verify_batch(tmv_ctx *ctx, const uint8_t *pk, const uint8_t *sig, const uint8_t *msg,
                                           const uint32_t *msg_off, uint32_t n, uint8_t *valid_out)
     __attribute__((weak));
+extern "C" int tmv_secp256k1_verify_batch_ex(tmv_ctx *ctx, uint32_t flags, const uint8_t *pk, const uint8_t *sig,
+                                             const uint8_t *msg, const uint32_t *msg_off, uint32_t n,
+                                             uint8_t *valid_out) __attribute__((weak));
 
 namespace {
 
@@ -302,10 +305,13 @@ int tmv_verify_extended_votes(tmv_ctx *ctx, int mode, const char *chain_id, cons
         const int rc = tmv_verify_batch_ex(ctx, k, TMV_FLAG_KEY_CACHE, pk.data(), sig.data(), msg.data(), off.data(),
                                            (uint32_t)m, st.data());
         if (rc < 0) return rc;
-      } else if (tmv_secp256k1_verify_batch) {  // the device entry (libtmgpu.so: always)
+      } else if (tmv_secp256k1_verify_batch_ex || tmv_secp256k1_verify_batch) {  // the device entry (libtmgpu.so: always)
         std::vector<uint8_t> valid(m, 0);
-        const int rc = tmv_secp256k1_verify_batch(ctx, pk.data(), sig.data(), msg.data(), off.data(), (uint32_t)m,
-                                                  valid.data());
+        const int rc = tmv_secp256k1_verify_batch_ex  // validators' keys cached
+                           ? tmv_secp256k1_verify_batch_ex(ctx, TMV_FLAG_KEY_CACHE, pk.data(), sig.data(), msg.data(),
+                                                           off.data(), (uint32_t)m, valid.data())
+                           : tmv_secp256k1_verify_batch(ctx, pk.data(), sig.data(), msg.data(), off.data(),
+                                                        (uint32_t)m, valid.data());
         if (rc < 0) return rc;
         for (size_t t = 0; t < m; t++) st[t] = (int8_t)valid[t];
       } else {  // no engine linked (the CPU test double): the same header's host build

@@ -701,10 +701,29 @@ TMV_HD void verify_prepare(VerifyInput &in, ge &q, uint32_t prefix, const uint32
   for (int k = 0; k < 7; k++) in.pad[k] = 0;
 }
 
+// x(R') mod n == r for a Jacobian R' (steps 7-8): r Z^2 == X or, when
+// r + n < p, (r + n) Z^2 == X.
+TMV_HD bool verify_compare(const VerifyInput &in, const gej &acc) {
+  // p - n = 0x14551231950b75fc4402da1722fc9baee: r + n < p iff r < p - n
+  const uint32_t pmn[8] = {0x2FC9BAEEu, 0x402DA172u, 0x50B75FC4u, 0x45512319u, 1u, 0u, 0u, 0u};
+  uint32_t nw[8];
+#pragma unroll
+  for (int k = 0; k < 8; k++) nw[k] = n_word(k);
+  fe fr, fn, z2, t;
+  fe_from_words(fr, in.r);
+  fe_from_words(fn, nw);
+  fe_sq(z2, acc.z);
+  fe_mul(t, fr, z2);               // 1
+  bool match = fe_equal(acc.x, t, 1);
+  fe_add(fr, fr, fn);              // 2: r + n, its true value when that is < p
+  fe_mul(t, fr, z2);
+  match = match || (words_less(in.r, pmn) && fe_equal(acc.x, t, 1));
+  return in.ok != 0 && !acc.inf && match;
+}
+
 // Steps 6-8: R' = u1 G + u2 Q by interleaved 4-bit windows (Straus): 64 steps
 // of four doublings, one mixed addition from the G table and one addition
-// from the signature's Q table; then x(R') mod n == r in Jacobian form,
-// r Z^2 == X or, when r + n < p, (r + n) Z^2 == X.  gtab / qtab as above.
+// from the signature's Q table; then the compare.  gtab / qtab as above.
 TMV_HD bool verify_chain(const VerifyInput &in, const uint32_t *gtab, const uint32_t *qtab) {
   gej acc;
   gej_set_infinity(acc);
@@ -726,21 +745,141 @@ TMV_HD bool verify_chain(const VerifyInput &in, const uint32_t *gtab, const uint
     qj.inf = d2 == 0;
     gej_add(acc, acc, qj);
   }
-  // p - n = 0x14551231950b75fc4402da1722fc9baee: r + n < p iff r < p - n
-  const uint32_t pmn[8] = {0x2FC9BAEEu, 0x402DA172u, 0x50B75FC4u, 0x45512319u, 1u, 0u, 0u, 0u};
-  uint32_t nw[8];
+  return verify_compare(in, acc);
+}
+
+// ------------------------------------------------------------------ comb tables
+// A cached key Q (and, once per context, G) is kept as a 4-bit comb: the
+// affine multiples d 16^j Q for window j = 0..63 and digit d = 1..15, so
+// u Q = sum_j comb[j][nibble_j(u)] needs 64 mixed additions and no doublings.
+// No entry is infinity: d 16^j <= 15 * 16^63 < n and Q has order n.  Entry
+// (j, d) is 16 words at kCombEntryWords * (15 j + d - 1): x then y as 8
+// little-endian words each, canonical (< p) -- 64 bytes, half a cache line,
+// 61,440 bytes per key.
+constexpr int kCombWindows = 64;
+constexpr int kCombEntryWords = 16;
+constexpr int kCombEntries = kCombWindows * kWindowEntries;   // 960
+constexpr int kCombWords = kCombEntries * kCombEntryWords;    // 15,360
+constexpr size_t kCombBytes = 4ull * kCombWords;              // 61,440
+
+// out[16 k ...] <- pts[k] in affine form, k < n, with one inversion for all
+// of them (Montgomery's trick: prefix products of the z, one fe_inv, and the
+// walk back).  No point may be infinity.  pre: n field elements of scratch.
+TMV_HD void comb_store_affine(uint32_t *out, const gej *pts, fe *pre, int n) {
+  pre[0] = pts[0].z;
+#pragma unroll 1
+  for (int k = 1; k < n; k++) fe_mul(pre[k], pre[k - 1], pts[k].z);
+  fe inv;
+  fe_inv(inv, pre[n - 1]);  // 1 / (z_0 ... z_{n-1})
+#pragma unroll 1
+  for (int k = n - 1; k >= 0; k--) {
+    fe zi, zi2, zi3, x, y;
+    if (k) {
+      fe_mul(zi, inv, pre[k - 1]);  // 1 / z_k
+      fe_mul(inv, inv, pts[k].z);   // 1 / (z_0 ... z_{k-1})
+    } else {
+      zi = inv;
+    }
+    fe_sq(zi2, zi);
+    fe_mul(zi3, zi2, zi);
+    fe_mul(x, pts[k].x, zi2);
+    fe_mul(y, pts[k].y, zi3);
+    fe_normalize(x);
+    fe_normalize(y);
+    fe_to_words_normalized(out + kCombEntryWords * k, x);
+    fe_to_words_normalized(out + kCombEntryWords * k + 8, y);
+  }
+}
+
+// pts[0..15) <- d base, d = 1..15.  Each step is the complete addition: 2 base
+// is the doubling it selects.
+TMV_HD void comb_window_multiples(gej *pts, const gej &base) {
+  pts[0] = base;
+#pragma unroll 1
+  for (int d = 1; d < kWindowEntries; d++) gej_add_any<false>(pts[d], pts[d - 1], base);
+}
+
+// The whole comb of q on one thread, one inversion per key (host: the G comb
+// at context init, the tests; the device builds one window per lane,
+// k_secp_key_table).  tab: kCombWords words.
+inline void build_comb(uint32_t *tab, const ge &q) {
+  gej *pts = new gej[kCombEntries];
+  fe *pre = new fe[kCombEntries];
+  gej base;
+  gej_set_ge(base, q);
+  for (int j = 0; j < kCombWindows; j++) {
+    comb_window_multiples(pts + kWindowEntries * j, base);
+    for (int k = 0; k < 4; k++) gej_double(base, base);
+  }
+  comb_store_affine(tab, pts, pre, kCombEntries);
+  delete[] pts;
+  delete[] pre;
+}
+
+// Comb entry (j, d) as an addend; d = 0 reads entry (j, 1) and is flagged
+// infinity, so every lane loads 64 bytes whatever its digit.
+TMV_HD void comb_load(gej &b, const uint32_t *tab, int j, uint32_t d) {
+  const uint32_t *e = static_cast<const uint32_t *>(
+      __builtin_assume_aligned(tab + kCombEntryWords * (kWindowEntries * j + (int)(d ? d - 1 : 0)), 16));
+  uint32_t w[16];
 #pragma unroll
-  for (int k = 0; k < 8; k++) nw[k] = n_word(k);
-  fe fr, fn, z2, t;
-  fe_from_words(fr, in.r);
-  fe_from_words(fn, nw);
-  fe_sq(z2, acc.z);
-  fe_mul(t, fr, z2);               // 1
-  bool match = fe_equal(acc.x, t, 1);
-  fe_add(fr, fr, fn);              // 2: r + n, its true value when that is < p
-  fe_mul(t, fr, z2);
-  match = match || (words_less(in.r, pmn) && fe_equal(acc.x, t, 1));
-  return in.ok != 0 && !acc.inf && match;
+  for (int k = 0; k < 16; k++) w[k] = e[k];
+  fe_from_words(b.x, w);
+  fe_from_words(b.y, w + 8);
+  fe_set_int(b.z, 1);
+  b.inf = d == 0;
+}
+
+// Steps 2-6 without the key work (k_secp_prep_cached): the range tests,
+// w = 1/s, u1 = z w, u2 = r w.  key_ok: the key parsed and has a comb.
+TMV_HD void verify_prepare_cached(VerifyInput &in, bool key_ok, const uint32_t rw[8], const uint32_t sw[8],
+                                  const uint32_t zw[8]) {
+  sc r, s, z, w;
+  bool ok = sc_below_n(rw) && key_ok;
+  ok = sc_below_n(sw) && ok;
+  sc_reduce_once(r, rw);
+  sc_reduce_once(s, sw);
+  ok = ok && !sc_is_zero(r) && !sc_is_zero(s) && !sc_is_high(s);
+  uint32_t zl[8];
+#pragma unroll
+  for (int k = 0; k < 8; k++) zl[k] = zw[7 - k];
+  sc_reduce_once(z, zl);  // z < 2^256 < 2n
+  sc_inv(w, s);
+  sc_mul(in.u1, z, w);
+  sc_mul(in.u2, r, w);
+#pragma unroll
+  for (int k = 0; k < 8; k++) in.r[k] = r.w[k];
+  in.ok = ok ? 1u : 0u;
+#pragma unroll
+  for (int k = 0; k < 7; k++) in.pad[k] = 0;
+}
+
+// R' = u1 G + u2 Q from the two combs: 128 complete mixed additions, window 63
+// first, G's entry then Q's, and no doublings of the accumulator.  The caller
+// of a verification chooses Q, r and s, so the accumulator can meet its own
+// addend (Q = G with equal leading digits), its negative, or infinity:
+// gej_add_any<true> takes every case by conditional moves.  rec: the
+// signature's VerifyInput record in memory (32 words).  The digits are read
+// from it window by window and r only for the compare, so the accumulator is
+// all a lane keeps in registers and nothing of it is indexed at run time.
+TMV_HD bool verify_chain_comb(const uint32_t *rec, const uint32_t *gcomb, const uint32_t *qcomb) {
+  gej acc;
+  gej_set_infinity(acc);
+#pragma unroll 1
+  for (int j = kCombWindows - 1; j >= 0; j--) {
+#pragma unroll 1
+    for (int h = 0; h < 2; h++) {  // one copy of the addition's code
+      const uint32_t d = (rec[8 * h + (j >> 3)] >> (4 * (j & 7))) & 15u;
+      gej e;
+      comb_load(e, h ? qcomb : gcomb, j, d);
+      gej_add_any<true>(acc, acc, e);
+    }
+  }
+  VerifyInput in;
+#pragma unroll
+  for (int k = 0; k < 8; k++) in.r[k] = rec[16 + k];
+  in.ok = rec[24];
+  return verify_compare(in, acc);
 }
 
 // SHA-256 of a message held in ordinary memory -> 8 state words
@@ -790,6 +929,43 @@ inline bool secp256k1_verify(const uint8_t pk33[33], const uint8_t z32[32], cons
   for (int k = 0; k < kQEntryWords; k++) qtab[k] = 0;
   build_q_table(qtab, q);
   return verify_chain(in, g.w, qtab);
+}
+
+// The same verdict through the combs, as the cached device path computes it
+// (host: the tests of that path's arithmetic).  build_key_comb is
+// k_secp_key_table's work for one key: false when the key does not parse (tab
+// then holds G's comb, as a slot would); secp256k1_verify_comb is
+// k_secp_prep_cached and k_secp_verify_comb for one signature.
+inline const uint32_t *g_comb_host() {
+  static const struct GComb {
+    uint32_t *w;
+    GComb() : w(new uint32_t[kCombWords]) {
+      ge g;
+      ge_generator(g);
+      build_comb(w, g);
+    }
+    ~GComb() { delete[] w; }
+  } g;
+  return g.w;
+}
+inline bool build_key_comb(uint32_t *tab, const uint8_t pk33[33]) {
+  uint32_t xw[8];
+  words_from_be32(xw, pk33 + 1);
+  ge q;
+  const bool ok = ge_decompress(q, pk33[0], xw);
+  build_comb(tab, q);
+  return ok;
+}
+inline bool secp256k1_verify_comb(bool key_ok, const uint32_t *qcomb, const uint8_t z32[32], const uint8_t sig64[64]) {
+  static_assert(sizeof(VerifyInput) == 128, "the record is 32 words");
+  uint32_t rw[8], sw[8], zl[8], zw[8];
+  words_from_be32(rw, sig64);
+  words_from_be32(sw, sig64 + 32);
+  words_from_be32(zl, z32);
+  for (int k = 0; k < 8; k++) zw[k] = zl[7 - k];
+  VerifyInput in;
+  verify_prepare_cached(in, key_ok, rw, sw, zw);
+  return verify_chain_comb(reinterpret_cast<const uint32_t *>(&in), g_comb_host(), qcomb);
 }
 
 // PubKey.VerifySignature(msg, sig) on the host (secp256k1.go:206-226)

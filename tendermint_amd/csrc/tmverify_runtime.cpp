@@ -256,6 +256,32 @@ struct Device {
   DeviceBuf d_valset, h_valset;  // tmv_validator_set_hashes staging
   uint32_t *d_secp_gtab = nullptr;             // secp256k1: j G, j = 1..15, affine (secp256k1.h)
   DeviceBuf d_secp_in, h_secp_in, d_secp_work; // tmv_secp256k1_verify_batch staging and workspace
+  // secp256k1 key cache (secp256k1.h, comb tables): device slots of 61,440
+  // bytes and a host LRU index, apart from the ed25519/sr25519 one above
+  // because the entries differ in size.  Device 0 only.
+  struct SecpKeys {
+    uint32_t *d_gcomb = nullptr;   // G's comb, built by the host at context init
+    uint32_t *d_tab = nullptr;     // cap slots; allocated at the first cached call
+    uint32_t *d_ok = nullptr;      // per slot: its key parsed (k_secp_key_table)
+    uint32_t cap = 0;              // TMV_SECP_KEY_CACHE_CAPACITY; 0 = off
+    bool tried = false;            // the allocation was attempted (a failure leaves the path off)
+    KeyIndex index;                // key bytes -> slot
+    std::list<uint32_t> lru;       // front = most recently used
+    std::vector<std::list<uint32_t>::iterator> pos;
+    std::vector<std::array<uint8_t, 33>> slot_key;
+    std::vector<uint64_t> slot_epoch;  // the call that last used the slot: never evicted by that call
+    std::vector<uint32_t> free_slots;  // taken back from keys that did not parse
+    KeyIndex bad;                  // keys the build kernel could not parse (host only, at most cap): no rebuild
+    uint32_t next_slot = 0;
+    uint64_t epoch = 0, hits = 0, misses = 0;
+    std::vector<uint32_t> slots, miss_entry, miss_slot, miss_ok;  // per call
+    void forget() {  // after a failed call the slots' contents are unknown
+      if (!index.t.empty()) index.init(cap);
+      lru.clear();
+      free_slots.clear();
+      next_slot = 0;
+    }
+  } sk;
   // host-buffer launches: key slots of the shard and the per-chunk key
   // histograms of the key-merged form's counting sort
   std::vector<uint32_t> slots, key_count;
@@ -876,6 +902,20 @@ static int init_device(Device &d) {
     e = hipMemcpy(d.d_bcomb, bc.data(), bc.size() * sizeof(tmv::fe), hipMemcpyHostToDevice);
     if (e != hipSuccess) { set_error("hipMemcpy(bcomb)", e); return TMV_ERR_NO_DEVICE; }
   }
+  {  // secp256k1 G comb (cached-key path), from the same header the kernels use
+    std::vector<uint32_t> gc(tmv::secp::kCombWords);
+    tmv::secp::ge g;
+    tmv::secp::ge_generator(g);
+    tmv::secp::build_comb(gc.data(), g);
+    e = hipMalloc(&d.sk.d_gcomb, tmv::secp::kCombBytes);
+    if (e != hipSuccess) { set_error("hipMalloc(secp gcomb)", e); return TMV_ERR_NOMEM; }
+    e = hipMemcpy(d.sk.d_gcomb, gc.data(), tmv::secp::kCombBytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { set_error("hipMemcpy(secp gcomb)", e); return TMV_ERR_NO_DEVICE; }
+  }
+  // 4,096 keys as the ed25519 cache (voi's LRU size): 240 MiB of device
+  // memory, allocated at the first cached secp256k1 call
+  const char *skc = getenv("TMV_SECP_KEY_CACHE_CAPACITY");
+  d.sk.cap = skc ? (uint32_t)std::min<unsigned long>(strtoul(skc, nullptr, 10), 1ul << 20) : 4096u;
   const char *kc = getenv("TMV_KEY_CACHE_CAPACITY");
   d.kcap = kc ? (uint32_t)strtoul(kc, nullptr, 10) : 4096u;  // voi's LRU size (crypto/ed25519/ed25519.go:56)
   const char *ps = getenv("TMV_POINT_CACHE_SLOTS");
@@ -1453,6 +1493,9 @@ int tmv_kernel_timing_read(tmv_ctx *ctx, const char *kernel, double *total_ms, u
   else if (!strcmp(kernel, "k_prep_fused")) k = tmv::ktimer::kPrep;
   else if (!strcmp(kernel, "k_secp_prep")) k = tmv::ktimer::kSecpPrep;
   else if (!strcmp(kernel, "k_secp_verify")) k = tmv::ktimer::kSecpVerify;
+  else if (!strcmp(kernel, "k_secp_key_table")) k = tmv::ktimer::kSecpKeyTable;
+  else if (!strcmp(kernel, "k_secp_prep_cached")) k = tmv::ktimer::kSecpPrepCached;
+  else if (!strcmp(kernel, "k_secp_verify_comb")) k = tmv::ktimer::kSecpVerifyComb;
   else if (!strcmp(kernel, "k_merkle_leaves_long")) k = tmv::ktimer::kMerkleLeavesLong;
   else if (!strcmp(kernel, "k_merkle_tree_levels")) k = tmv::ktimer::kMerkleTreeLevels;
   else if (!strcmp(kernel, "k_merkle_aunts")) k = tmv::ktimer::kMerkleAunts;
@@ -1618,6 +1661,9 @@ void tmv_close(tmv_ctx *ctx) {
     if (d->kbuild_copied) (void)hipEventDestroy(d->kbuild_copied);
     if (d->d_btable) (void)hipFree(d->d_btable);
     if (d->d_secp_gtab) (void)hipFree(d->d_secp_gtab);
+    if (d->sk.d_gcomb) (void)hipFree(d->sk.d_gcomb);
+    if (d->sk.d_tab) (void)hipFree(d->sk.d_tab);
+    if (d->sk.d_ok) (void)hipFree(d->sk.d_ok);
     d->d_secp_in.release();
     d->h_secp_in.release();
     d->d_secp_work.release();
@@ -2653,12 +2699,133 @@ int tmv_merkle_roots(tmv_ctx *ctx, const uint8_t *data, const uint32_t *leaf_off
   return 0;
 }
 
+}  // extern "C"
+
+// secp256k1 key cache: the slot of every entry of one call, allocating slots
+// (and evicting least recently used keys) for the keys it has not seen.
+// Returns 1 if the cached path is not available for this call -- the cache is
+// off, its table found no room, or the call has more distinct keys than the
+// cache holds -- and the caller takes the uncached path; 0 with sk.slots (n
+// entries) and sk.miss_entry / sk.miss_slot (an entry holding each key to
+// build, and its slot) filled.  A key whose prefix or x range cannot parse
+// gets kSecpNoSlot here; one whose x^3 + 7 is no square is found by the build
+// kernel, its slot taken back by secp_keys_settle and the key remembered on
+// the host (sk.bad), so later calls give it kSecpNoSlot without a build.  The
+// caller holds d.mu and has waited for the stream, so no launch is reading a
+// slot.
+static int secp_keys_resolve(Device &d, const uint8_t *pk, uint32_t n) {
+  Device::SecpKeys &k = d.sk;
+  if (k.cap == 0) return 1;
+  if (!k.tried) {
+    k.tried = true;
+    if (hipMalloc(&k.d_tab, (size_t)k.cap * tmv::secp::kCombBytes) != hipSuccess) {
+      (void)hipGetLastError();
+      k.d_tab = nullptr;
+    } else if (hipMalloc(&k.d_ok, 4ull * k.cap) != hipSuccess) {
+      (void)hipGetLastError();
+      (void)hipFree(k.d_tab);
+      k.d_tab = nullptr;
+      k.d_ok = nullptr;
+    } else {
+      k.pos.resize(k.cap);
+      k.slot_key.resize(k.cap);
+      k.slot_epoch.assign(k.cap, 0);
+      k.index.init(k.cap);
+      k.bad.init(k.cap);
+    }
+  }
+  if (!k.d_tab) return 1;
+  constexpr uint32_t kNew = 0x80000000u;  // slots[i] = kNew | ordinal of a key not seen before
+  const uint64_t epoch = ++k.epoch;
+  k.slots.resize(n);
+  k.miss_entry.clear();
+  k.miss_slot.clear();
+  std::vector<uint32_t> hit_slots;
+  KeyIndex fresh;  // new key -> ordinal in miss_entry
+  fresh.init(std::min<size_t>(n, (size_t)k.cap + 1));
+  uint32_t pw[8];
+  for (int w = 0; w < 8; w++) pw[w] = tmv::secp::p_word(w);
+  const uint8_t *last = nullptr;
+  for (uint32_t i = 0; i < n; i++) {
+    const uint8_t *p = pk + 33ull * i;
+    if (last && std::memcmp(p, last, 33) == 0) { k.slots[i] = k.slots[i - 1]; continue; }
+    last = p;
+    uint32_t slot = k.index.find(p);
+    if (slot != UINT32_MAX) {
+      if (k.slot_epoch[slot] != epoch) { k.slot_epoch[slot] = epoch; hit_slots.push_back(slot); }
+      k.slots[i] = slot;
+      continue;
+    }
+    uint32_t xw[8];
+    tmv::secp::words_from_be32(xw, p + 1);
+    if ((p[0] != 2 && p[0] != 3) || !tmv::secp::words_less(xw, pw) || k.bad.find(p) != UINT32_MAX) {
+      k.slots[i] = tmv::kSecpNoSlot;
+      continue;
+    }
+    uint32_t ord = fresh.find(p);
+    if (ord == UINT32_MAX) {
+      ord = (uint32_t)k.miss_entry.size();
+      if (hit_slots.size() + ord + 1 > k.cap) return 1;  // no index entry changed yet
+      fresh.insert(p, ord);
+      k.miss_entry.push_back(i);
+    }
+    k.slots[i] = kNew | ord;
+  }
+  if (hit_slots.size() + k.miss_entry.size() > k.cap) return 1;
+  for (uint32_t slot : hit_slots) {
+    k.lru.splice(k.lru.begin(), k.lru, k.pos[slot]);
+    k.hits++;
+  }
+  for (uint32_t i : k.miss_entry) {
+    uint32_t slot;
+    if (!k.free_slots.empty()) {
+      slot = k.free_slots.back();
+      k.free_slots.pop_back();
+      k.lru.push_front(slot);
+    } else if (k.next_slot < k.cap) {
+      slot = k.next_slot++;
+      k.lru.push_front(slot);
+    } else {
+      slot = k.lru.back();  // least recently used; this call's slots are all ahead of it
+      k.index.erase(k.slot_key[slot].data());
+      k.lru.splice(k.lru.begin(), k.lru, k.pos[slot]);
+    }
+    k.pos[slot] = k.lru.begin();
+    std::memcpy(k.slot_key[slot].data(), pk + 33ull * i, 33);
+    k.slot_epoch[slot] = epoch;
+    k.index.insert(pk + 33ull * i, slot);
+    k.miss_slot.push_back(slot);
+    k.misses++;
+  }
+  for (uint32_t i = 0; i < n; i++)
+    if (k.slots[i] != tmv::kSecpNoSlot && (k.slots[i] & kNew)) k.slots[i] = k.miss_slot[k.slots[i] & ~kNew];
+  return 0;
+}
+
+// After a cached call's device work: the keys the build kernel could not
+// parse (sk.miss_ok) give their slots back and count as neither hit nor miss.
+static void secp_keys_settle(Device &d) {
+  Device::SecpKeys &k = d.sk;
+  for (size_t m = 0; m < k.miss_slot.size(); m++) {
+    if (k.miss_ok[m]) continue;
+    const uint32_t slot = k.miss_slot[m];
+    k.index.erase(k.slot_key[slot].data());
+    k.lru.erase(k.pos[slot]);
+    k.free_slots.push_back(slot);
+    k.misses--;
+    if (k.bad.size() >= k.cap) k.bad.init(k.cap);
+    k.bad.insert(k.slot_key[slot].data(), 0);
+  }
+}
+
 // secp256k1 ECDSA batch (crypto/secp256k1/secp256k1.go:206-226 per entry).
 // Synchronous, host buffers, device 0; staged like tmv_merkle_roots: one H2D
-// copy (keys padded to 48 bytes), the launches (in chunks that bound the Q
-// table workspace), one D2H copy.
-int tmv_secp256k1_verify_batch(tmv_ctx *ctx, const uint8_t *pk, const uint8_t *sig, const uint8_t *msg,
-                               const uint32_t *msg_off, uint32_t n, uint8_t *valid_out) {
+// copy (keys padded to 48 bytes), the launches (in chunks that bound the
+// workspace), one D2H copy.  cache: verify against the keys' combs on the
+// device (secp_keys_resolve), building the missing ones on the same stream
+// ahead of the verification; the staging then carries slots in place of keys.
+static int secp256k1_batch(tmv_ctx *ctx, bool cache, const uint8_t *pk, const uint8_t *sig, const uint8_t *msg,
+                           const uint32_t *msg_off, uint32_t n, uint8_t *valid_out) {
   if (!ctx || ctx->devs.empty()) { set_error("null context"); return TMV_ERR_ARG; }
   if (n == 0) return TMV_NOT_ALL;
   if (!pk || !sig || !msg_off || !valid_out) { set_error("tmv_secp256k1_verify_batch: null pointer"); return TMV_ERR_ARG; }
@@ -2675,23 +2842,45 @@ int tmv_secp256k1_verify_batch(tmv_ctx *ctx, const uint8_t *pk, const uint8_t *s
   if (d.faulted) return faulted_rc(d);
   hipError_t e = hipSetDevice(d.id);
   if (e != hipSuccess) { set_error("hipSetDevice", e); return TMV_ERR_NO_DEVICE; }
-  // staging: pk48 | sig | msg_off | msg, then (device only) the statuses
-  constexpr uint32_t kChunk = 262144;  // entries per launch pair: 2,176 bytes of workspace each
-  const size_t o_sig = 48ull * n, o_off = o_sig + 64ull * n, o_msg = o_off + align16(4ull * (n + 1));
-  const size_t in_bytes = o_msg + align16(bytes), o_out = in_bytes, dev_bytes = o_out + align16(n);
+  constexpr uint32_t kChunk = 262144;  // entries per launch pair: 2,176 bytes of workspace each (cached: 128)
   hipStream_t s = context_stream(d);
   if (!s) { set_error("hipStreamCreate failed"); return TMV_ERR_NO_DEVICE; }
-  if ((e = wait_stream(d, s)) != hipSuccess) return wait_rc(e);  // staging may still feed an earlier call
+  // staging may still feed an earlier call; and with the stream idle no launch
+  // reads a key slot that a miss of this call may evict
+  if ((e = wait_stream(d, s)) != hipSuccess) return wait_rc(e);
+  cache = cache && secp_keys_resolve(d, pk, n) == 0;
+  Device::SecpKeys &k = d.sk;
+  const uint32_t nm = cache ? (uint32_t)k.miss_entry.size() : 0;
+  // staging: [pk48 |] sig | msg_off | msg [| slots | missing keys at 48 | their slots], then (device only) the
+  // statuses [and the missing keys' parse flags]
+  const size_t o_sig = cache ? 0 : 48ull * n, o_off = o_sig + 64ull * n, o_msg = o_off + align16(4ull * (n + 1));
+  const size_t o_slot = o_msg + align16(bytes), o_mpk = o_slot + (cache ? align16(4ull * n) : 0);
+  const size_t o_mslot = o_mpk + 48ull * nm, in_bytes = o_mslot + align16(4ull * nm);
+  const size_t o_out = in_bytes, o_mok = o_out + align16(n), dev_bytes = o_mok + align16(4ull * nm);
+  // a failure from here on leaves this call's new slots unbuilt: drop the index
+  struct Guard {
+    Device::SecpKeys *k;
+    ~Guard() { if (k) k->forget(); }
+  } guard{cache ? &k : nullptr};
   if ((e = d.h_secp_in.ensure(in_bytes, true)) != hipSuccess) { set_error("hipHostMalloc", e); return TMV_ERR_NOMEM; }
   if ((e = d.d_secp_in.ensure(dev_bytes, false)) != hipSuccess) { set_error("hipMalloc", e); return TMV_ERR_NOMEM; }
-  if ((e = d.d_secp_work.ensure(tmv::secp256k1_workspace_bytes(std::min(n, kChunk)), false)) != hipSuccess) {
+  const uint32_t cn = std::min(n, kChunk);
+  const size_t work_bytes = cache ? tmv::secp256k1_cached_workspace_bytes(cn) : tmv::secp256k1_workspace_bytes(cn);
+  if ((e = d.d_secp_work.ensure(work_bytes, false)) != hipSuccess) {
     set_error("hipMalloc(secp work)", e);
     return TMV_ERR_NOMEM;
   }
   uint8_t *h = static_cast<uint8_t *>(d.h_secp_in.ptr);
-  for (uint32_t i = 0; i < n; i++) {
-    std::memcpy(h + 48ull * i, pk + 33ull * i, 33);
-    std::memset(h + 48ull * i + 33, 0, 15);
+  auto pad_key = [](uint8_t *dst, const uint8_t *src) {
+    std::memcpy(dst, src, 33);
+    std::memset(dst + 33, 0, 15);
+  };
+  if (cache) {
+    std::memcpy(h + o_slot, k.slots.data(), 4ull * n);
+    for (uint32_t m = 0; m < nm; m++) pad_key(h + o_mpk + 48ull * m, pk + 33ull * k.miss_entry[m]);
+    if (nm) std::memcpy(h + o_mslot, k.miss_slot.data(), 4ull * nm);
+  } else {
+    for (uint32_t i = 0; i < n; i++) pad_key(h + 48ull * i, pk + 33ull * i);
   }
   std::memcpy(h + o_sig, sig, 64ull * n);
   std::memcpy(h + o_off, msg_off, 4ull * (n + 1));
@@ -2701,21 +2890,65 @@ int tmv_secp256k1_verify_batch(tmv_ctx *ctx, const uint8_t *pk, const uint8_t *s
     set_error("hipMemcpyAsync(secp256k1)", e);
     return TMV_ERR_LAUNCH;
   }
+  if (nm) {
+    e = tmv::launch_secp256k1_key_tables(g + o_mpk, reinterpret_cast<const uint32_t *>(g + o_mslot), nm, k.d_tab,
+                                         k.d_ok, reinterpret_cast<uint32_t *>(g + o_mok), s);
+    if (e != hipSuccess) { set_error("secp256k1 key table launch", e); return TMV_ERR_LAUNCH; }
+  }
   for (uint32_t lo = 0; lo < n; lo += kChunk) {
     const uint32_t m = std::min(kChunk, n - lo);
-    e = tmv::launch_secp256k1_verify(g + 48ull * lo, g + o_sig + 64ull * lo, g + o_msg,
-                                     reinterpret_cast<const uint32_t *>(g + o_off) + lo, m, d.d_secp_gtab,
-                                     static_cast<uint8_t *>(d.d_secp_work.ptr), g + o_out + lo, s);
+    const uint32_t *off = reinterpret_cast<const uint32_t *>(g + o_off) + lo;
+    uint8_t *work = static_cast<uint8_t *>(d.d_secp_work.ptr);
+    if (cache)
+      e = tmv::launch_secp256k1_verify_cached(g + o_sig + 64ull * lo, g + o_msg, off,
+                                              reinterpret_cast<const uint32_t *>(g + o_slot) + lo, m, k.d_gcomb,
+                                              k.d_tab, k.d_ok, work, g + o_out + lo, s);
+    else
+      e = tmv::launch_secp256k1_verify(g + 48ull * lo, g + o_sig + 64ull * lo, g + o_msg, off, m, d.d_secp_gtab, work,
+                                       g + o_out + lo, s);
     if (e != hipSuccess) { set_error("secp256k1 launch", e); return TMV_ERR_LAUNCH; }
+  }
+  if (nm) {
+    k.miss_ok.assign(nm, 0);
+    if ((e = hipMemcpyAsync(k.miss_ok.data(), g + o_mok, 4ull * nm, hipMemcpyDeviceToHost, s)) != hipSuccess) {
+      set_error("secp256k1 readback", e);
+      return TMV_ERR_LAUNCH;
+    }
   }
   if ((e = hipMemcpyAsync(valid_out, g + o_out, n, hipMemcpyDeviceToHost, s)) != hipSuccess ||
       (e = wait_stream(d, s)) != hipSuccess) {
     if (e != hipErrorNotReady) set_error("secp256k1 readback", e);
     return wait_rc(e);
   }
+  guard.k = nullptr;
+  if (nm) secp_keys_settle(d);
   bool all = true;
   for (uint32_t i = 0; i < n; i++) all = all && valid_out[i] == 1;
   return all ? TMV_ALL_VALID : TMV_NOT_ALL;
+}
+
+extern "C" {
+
+int tmv_secp256k1_verify_batch(tmv_ctx *ctx, const uint8_t *pk, const uint8_t *sig, const uint8_t *msg,
+                               const uint32_t *msg_off, uint32_t n, uint8_t *valid_out) {
+  return secp256k1_batch(ctx, false, pk, sig, msg, msg_off, n, valid_out);
+}
+
+int tmv_secp256k1_verify_batch_ex(tmv_ctx *ctx, uint32_t flags, const uint8_t *pk, const uint8_t *sig,
+                                  const uint8_t *msg, const uint32_t *msg_off, uint32_t n, uint8_t *valid_out) {
+  if (flags & ~TMV_FLAG_KEY_CACHE) { set_error("tmv_secp256k1_verify_batch_ex: unknown flag"); return TMV_ERR_ARG; }
+  return secp256k1_batch(ctx, (flags & TMV_FLAG_KEY_CACHE) != 0, pk, sig, msg, msg_off, n, valid_out);
+}
+
+int tmv_secp256k1_key_cache_stats(tmv_ctx *ctx, uint64_t *hits, uint64_t *misses, uint32_t *used, uint32_t *capacity) {
+  if (!ctx || ctx->devs.empty()) return TMV_ERR_ARG;
+  Device &d = *ctx->devs[0];
+  std::lock_guard<std::mutex> lk(d.mu);
+  if (hits) *hits = d.sk.hits;
+  if (misses) *misses = d.sk.misses;
+  if (used) *used = (uint32_t)d.sk.index.size();
+  if (capacity) *capacity = d.sk.cap;
+  return 0;
 }
 
 }  // extern "C"

@@ -730,6 +730,25 @@ def verify_vote_batch(ctx, chain_id: str, votes: List[Vote], keys: List[Tuple[in
     return verify_vote_batch_call(L.tmv_verify_vote_batch, ctx.handle, chain_id, votes, keys)
 
 
+def verify_secp256k1_signatures(ctx, entries: List[Tuple[bytes, bytes, bytes]], key_cache: bool = True) -> List[bool]:
+    """PubKey.VerifySignature (crypto/secp256k1/secp256k1.go:206-226) for each (key33, msg, sig64) in one
+    engine call: tmv_secp256k1_verify_batch_ex with the keys' comb tables kept on the device, or (key_cache
+    false) tmv_secp256k1_verify_batch.  A key or signature of another size is False, as the reference's."""
+    import numpy as np
+    sized = [i for i, (pk, _, sig) in enumerate(entries) if len(pk) == 33 and len(sig) == 64]
+    out = [False] * len(entries)
+    if not sized:
+        return out
+    cat = lambda k: np.frombuffer(b"".join(entries[i][k] for i in sized), np.uint8).copy()  # noqa: E731
+    off = np.zeros(len(sized) + 1, np.uint32)
+    off[1:] = np.cumsum([len(entries[i][1]) for i in sized])
+    call = ctx.secp256k1_verify_batch_ex if key_cache else ctx.secp256k1_verify_batch
+    _, valid = call(cat(0), cat(2), cat(1), off)
+    for i, v in zip(sized, valid):
+        out[i] = bool(v)
+    return out
+
+
 # ---------------------------------------------------------------- vote extensions
 VOTE_MODE_VERIFY, VOTE_MODE_VERIFY_AND_EXTENSION, VOTE_MODE_EXTENSION = 0, 1, 2
 

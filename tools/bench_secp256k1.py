@@ -14,6 +14,16 @@ kernels keep nothing between entries, so repetition does not change their
 work).  Every run checks the verdicts against the batch's construction.
 
     python tools/bench_secp256k1.py [--out profiles/secp256k1/bench.json]
+
+--cached measures tmv_secp256k1_verify_batch_ex with TMV_FLAG_KEY_CACHE (the
+keys' comb tables kept on the device) against the uncached call instead: 150
+entries of 150 keys, 175 keys x 600, and the two shapes above, the two calls
+alternating in one session.  Per shape: the first cached call of a fresh
+context (it builds every key's table), then medians with their spread of the
+steady state (every key a hit) and of the uncached call, and the cached
+kernels' durations.
+
+    python tools/bench_secp256k1.py --cached [--out profiles/secp256k1_cache/bench.json]
 """
 import argparse
 import hashlib
@@ -65,6 +75,66 @@ def gpu_rates(ctx, b: F.SecpBatch, reps: int) -> dict:
             "end_to_end_verifies_per_s": b.n / med}
 
 
+def spread(xs) -> dict:
+    return {"median": float(np.median(xs)) * 1e3, "min": min(xs) * 1e3, "max": max(xs) * 1e3}
+
+
+def cached_row(name: str, b: F.SecpBatch, reps: int) -> dict:
+    """One shape, a context of its own: first cached call, then uncached and cached calls alternating."""
+    want = np.array([c == "honest" for c in b.category], np.uint8)
+    ctx = _native.Context(1)
+    try:
+        _, got = ctx.secp256k1_verify_batch(b.pk, b.sig, b.msg, b.off)  # warm-up: code objects, staging buffers
+        assert np.array_equal(got, want), "verdicts differ from the batch's construction"
+        t0 = time.perf_counter()
+        _, got = ctx.secp256k1_verify_batch_ex(b.pk, b.sig, b.msg, b.off)
+        first = time.perf_counter() - t0
+        assert np.array_equal(got, want), "cached verdicts differ from the batch's construction"
+        st0 = ctx.secp256k1_key_cache_stats()
+        plain, cached = [], []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            ctx.secp256k1_verify_batch(b.pk, b.sig, b.msg, b.off)
+            plain.append(time.perf_counter() - t0)
+            t0 = time.perf_counter()
+            _, got = ctx.secp256k1_verify_batch_ex(b.pk, b.sig, b.msg, b.off)
+            cached.append(time.perf_counter() - t0)
+            assert np.array_equal(got, want)
+        st1 = ctx.secp256k1_key_cache_stats()
+        assert st1["misses"] == st0["misses"] and st1["hits"] > st0["hits"], "the steady state was not all hits"
+        ctx.kernel_timing(True)
+        try:
+            for _ in range(reps):
+                ctx.secp256k1_verify_batch_ex(b.pk, b.sig, b.msg, b.off)
+                ctx.secp256k1_verify_batch(b.pk, b.sig, b.msg, b.off)
+            k = {n: ctx.kernel_timing_read(n) for n in ("k_secp_prep_cached", "k_secp_verify_comb", "k_secp_prep",
+                                                        "k_secp_verify")}
+        finally:
+            ctx.kernel_timing(False)
+        return {"shape": name, "n": b.n, "keys": st0["misses"], "reps": reps,
+                "first_cached_call_ms": first * 1e3, "cached_steady_ms": spread(cached), "uncached_ms": spread(plain),
+                "kernels_ms_per_call": {n: ms / reps for n, (ms, _) in k.items()},
+                "key_table_bytes": st0["used"] * 61440}
+    finally:
+        ctx.close()
+
+
+def cached_main(args):
+    import torch
+    fast = F.have_openssl()
+    base = F.make_secp_batch(args.base_n, seed=0xBE7C, bad_frac=0.01, keys=175, fast=fast)
+    shapes = [("150 entries x 150 keys", F.make_secp_batch(150, seed=0xC1, bad_frac=0.01, keys=150, fast=fast)),
+              ("175 keys x 600", F.make_secp_batch(175 * 600, seed=0xC4, bad_frac=0.01, keys=175, fast=fast)),
+              ("%d entries x 175 keys" % base.n, base), ("%d entries x 175 keys" % (10 * base.n), tile(base, 10))]
+    res = {"device": torch.cuda.get_device_name(0), "version": _native.version(),
+           "rows": [cached_row(name, b, args.reps) for name, b in shapes]}
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res))
+
+
 def openssl_rate(b: F.SecpBatch, threads: int, seconds: float) -> dict:
     """ECDSA_do_verify over the batch's honest entries on `threads` host threads
     (ctypes releases the interpreter lock during the call)."""
@@ -105,7 +175,8 @@ def openssl_rate(b: F.SecpBatch, threads: int, seconds: float) -> dict:
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "secp256k1", "bench.json"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--cached", action="store_true", help="cached vs uncached rows (see the module text)")
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--cpu-seconds", type=float, default=4.0)
@@ -114,6 +185,10 @@ def main():
     import torch
     if not torch.cuda.is_available():
         sys.exit("bench_secp256k1.py needs a GPU (there is no CPU fallback)")
+    if args.out is None:
+        args.out = os.path.join(REPO, "profiles", "secp256k1_cache" if args.cached else "secp256k1", "bench.json")
+    if args.cached:
+        return cached_main(args)
     t0 = time.perf_counter()
     base = F.make_secp_batch(args.base_n, seed=0xBE7C, bad_frac=0.01, keys=175, fast=F.have_openssl())
     gen_s = time.perf_counter() - t0
