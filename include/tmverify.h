@@ -335,6 +335,22 @@ int tmv_key_cache_stats(tmv_ctx *ctx, uint64_t *hits, uint64_t *misses, uint32_t
  * waited for the launches it wants counted. */
 int tmv_point_cache_stats(tmv_ctx *ctx, uint64_t *hits, uint64_t *misses, uint32_t *slots);
 
+/* Bucket entries the batch equation's sort placed (k_msm_sort, located pass
+ * included), cumulative over the launches of this context's devices made
+ * while TMV_BATCHOPT_STATS was set.  Entries per signature is the measure of
+ * how far runs of one key collapsed (multi-batch launches of one validator
+ * set's commits).  Read from the devices on this call only; the caller has
+ * waited for the launches it wants counted. */
+int tmv_bucket_entry_stats(tmv_ctx *ctx, uint64_t *entries);
+
+/* Group verdicts of the uncached batch-equation launches made while
+ * TMV_BATCHOPT_STATS was set, device-pointer launches included (which
+ * tmv_batch_stats does not see): groups that failed the equation, failing
+ * groups whose one bad entry the located pass named, and entries the located
+ * pass left to verify one by one.  Counted on the devices, read on this call
+ * only; the caller has waited for the launches it wants counted. */
+int tmv_group_fail_stats(tmv_ctx *ctx, uint64_t *groups_failed, uint64_t *groups_located, uint64_t *fallback_entries);
+
 /* Library metrics (verifies/s, batch size, fallback count, H2D
  * bytes -- the reference exports its own per package through Prometheus,
  * e.g. internal/consensus/metrics.gen.go; a Go shim would publish these).

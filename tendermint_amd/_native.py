@@ -55,7 +55,8 @@ EXPORTS = [
     "tmv_secp256k1_verify_batch", "tmv_secp256k1_verify", "tmv_secp256k1_verify_batch_ex",
     "tmv_secp256k1_key_cache_stats",
     "tmv_verify_mixed_batch", "tmv_ed25519_verify_batch_device", "tmv_verify_mixed_batch_device",
-    "tmv_verify_batch_ex", "tmv_key_cache_stats", "tmv_point_cache_stats", "tmv_set_batch_options", "tmv_batch_stats",
+    "tmv_verify_batch_ex", "tmv_key_cache_stats", "tmv_point_cache_stats", "tmv_bucket_entry_stats", "tmv_group_fail_stats",
+    "tmv_set_batch_options", "tmv_batch_stats",
     "tmv_subgroup_stats", "tmv_validator_set_hashes",
     "tmv_verify_mixed_batch_ex", "tmv_verify_batch_device_ex", "tmv_verify_batches_device",
     "tmv_verify_votes", "tmv_vote_sign_bytes_device", "tmv_verify_votes_and_extensions",
@@ -187,6 +188,8 @@ def lib() -> ctypes.CDLL:
                                           ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]
         L.tmv_point_cache_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
                                             ctypes.POINTER(ctypes.c_uint32)]
+        L.tmv_bucket_entry_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
+        L.tmv_group_fail_stats.argtypes = [vp] + [ctypes.POINTER(ctypes.c_uint64)] * 3
         L.tmv_set_batch_options.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, u8p, ctypes.c_uint32]
         L.tmv_batch_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
         L.tmv_kernel_timing.argtypes = [vp, ctypes.c_int]
@@ -650,6 +653,19 @@ class Context:
         self._check(self._lib.tmv_point_cache_stats(self._h, ctypes.byref(h), ctypes.byref(m), ctypes.byref(c)),
                     "tmv_point_cache_stats")
         return {"hits": h.value, "misses": m.value, "slots": c.value}
+
+    def bucket_entry_stats(self) -> int:
+        """Bucket entries sorted by the batch equation since stats were switched on (read from the devices now)."""
+        v = ctypes.c_uint64()
+        self._check(self._lib.tmv_bucket_entry_stats(self._h, ctypes.byref(v)), "tmv_bucket_entry_stats")
+        return v.value
+
+    def group_fail_stats(self) -> dict:
+        """Failing groups, located groups and entries left one by one of the stats launches (read from the devices now)."""
+        f, l, e = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        self._check(self._lib.tmv_group_fail_stats(self._h, ctypes.byref(f), ctypes.byref(l), ctypes.byref(e)),
+                    "tmv_group_fail_stats")
+        return {"failed": f.value, "located": l.value, "fallback_entries": e.value}
 
     def metrics(self) -> dict:
         """tmv_metrics: cumulative counters (plus verifies_per_s_host, the

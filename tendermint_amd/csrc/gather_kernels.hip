@@ -6,6 +6,7 @@
 // blocks would.  Pure data movement (HBM-bound).
 #include <hip/hip_runtime.h>
 #include "verify_kernels.h"
+#include "colorder.h"
 
 namespace tmv {
 
@@ -93,6 +94,26 @@ k_scatter(BatchRefs r, const int8_t *__restrict__ status) {
   if (e >= r.start[r.nb]) return;
   const uint32_t b = batch_of(r, e);
   r.out[b][e - r.start[b]] = status[e];
+}
+
+// Column order (colorder.h): lane e writes idx[slot of gathered entry e] = e.
+// The slot function is a bijection onto [0, N), so every idx word is written
+// once and slot < N.
+__global__ void __launch_bounds__(256)
+k_column_order(ColumnPlan c, uint32_t *__restrict__ idx) {
+  const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t N = c.start[c.K];
+  if (e >= N) return;
+  const uint32_t j = column_batch_of(c, e);
+  const uint32_t slot = column_slot(c, j, e - c.start[j]);
+  if (slot < N) idx[slot] = e;
+}
+
+hipError_t launch_column_order(const ColumnPlan &c, uint32_t *idx, hipStream_t stream) {
+  const uint32_t N = c.start[c.K];
+  if (N == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_column_order, dim3((N + 255) / 256), dim3(256), 0, stream, c, idx);
+  return hipGetLastError();
 }
 
 hipError_t launch_gather(const BatchRefs &r, uint8_t *pk, uint8_t *sig, uint32_t *off, uint8_t *msg,

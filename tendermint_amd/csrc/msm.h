@@ -27,6 +27,29 @@
 //   k_msm_horner one quad per group: T_g = sum_w 2^(c w) S_w (Horner, quad-lane
 //                arithmetic) and the group verdict
 //
+// Runs of one key (uncached ed25519 form; k_msm_sort): inside a group every
+// live entry whose 32-byte key encoding equals that of an earlier live entry
+// joins that entry's run, and the run's A terms are one term,
+//   sum_{i in run} [z_i k_i mod l](-A) -> [sum_{i in run} z_i k_i mod l](-A),
+// about W bucket entries for the run instead of W per signature.  Multi-batch
+// launches order their work slots down the columns of a tile of batches
+// (colorder.h), so that the commits of one validator set put long runs into
+// every group.  Why the validity vector stays what it was:
+//   - The merged scalar differs from the sum of the separate ones by a
+//     multiple of l, and [l](-A) lies in the torsion subgroup (A's order
+//     divides 8 l), so T_g is the same group element up to a point of order
+//     dividing 8.
+//   - The verdict ([8] T_g == O) and the located pass's search (k_loc_search:
+//     M = [8] T, M' = [8] T') both multiply by 8, which removes that point.
+//   - T_g is the same linear form in the z_i as before, so the false-accept
+//     bound per group (<= 2^-128) is unchanged.
+//   - The per-entry fallback reads each entry's own -A from the workspace
+//     (Ed25519Work::negA), which merging never touches.
+// Equality is decided on the full encoding (a 32-bit tag in LDS only finds
+// candidates); two encodings of one point simply do not merge.  Entries left
+// out of the sums stay out, and a run's first entry is always a live one.
+// sr25519, mixed launches and the key-merged form below are not merged here.
+//
 // Key-merged form (batches whose keys sit in the
 // device key cache, e.g. commits of one validator set): entries are ordered
 // by key, so a group holds few distinct keys, and the A terms collapse to
@@ -49,6 +72,7 @@ namespace tmv {
 constexpr uint32_t kMsmWideRows = 65536;     // (group, window) rows from which k_msm_wpart runs one lane per window
 constexpr int kMsmChunkMax = 32;             // sorted entries per accumulation lane: 16 or 32
 constexpr uint32_t kMsmEmpty = 0xffffffffu;  // padding entry / no bucket
+constexpr uint32_t kMsmCompactGroups = 2048; // groups from which k_msm_accum's lanes cover the live chunks only
 constexpr int kMsmSortBlock = 256;
 // Buckets cut by chunk edges are joined by k_msm_accum (neighbouring lanes of
 // a wave) and k_msm_join_list (the rest, from a packed list) before the
@@ -183,6 +207,10 @@ struct MsmWork {
                          // launch may run at once); reset by every k_msm_sort, appended by k_msm_accum
   ge_p3 *wpart;        // groups x W x P x 2: (T, U) of each window part
   ge_p3 *wsum;         // groups x W: window sums
+  uint32_t *grp_chunks;  // groups: chunks of the group that hold entries (k_msm_sort)
+  uint32_t *chunk_end;   // groups: inclusive prefix of grp_chunks over the live groups (k_msm_chunk_scan);
+                         // null in a launch below kMsmCompactGroups (set by launch_buckets)
+  uint32_t compact;      // 1: the accumulation will read the live chunks only (set by the sort's launch)
   uint8_t *group_ok;   // groups
   // 1 when a group's bucket entries would not fit its cap slots (cannot
   // happen: MsmParams::make bounds the digits; k_msm_sort then leaves the
@@ -203,6 +231,12 @@ struct MsmWork {
   uint32_t *fb_count;    // entries in fb_list
   uint32_t *loc_found;   // failing groups whose one bad entry the search named (tmv_metrics)
   uint32_t *fb_list;     // n: work indices verified one by one
+  // runs of one key (k_msm_sort, uncached ed25519 form): the key encodings the
+  // launch's entries index (pk of the launch or of the part), null = no
+  // merging; and the device's count of bucket entries sorted (null: not
+  // counted).  Both are set by the launch, not by carve.
+  const uint8_t *merge_pk;
+  unsigned long long *ent_total;  // [0] entries sorted, [1] failing groups, [2] located groups, [3] entries left one by one
   // key-merged form only (null otherwise)
   uint32_t *wscal;     // n x 8 words: z_e k_e mod l (0 for entries left out)
   uint32_t *bscal;     // groups x 8 words: B scalar of the group
@@ -216,7 +250,7 @@ struct MsmWork {
     const size_t chunks = ent / p.L;
     size_t b = (2ull * n + 1) * kNielsPer * sizeof(niels_pt) + 8 * ent + 8 * bk + bk * sizeof(ge_p3) +
                2 * chunks * sizeof(ge_p3) + 4 * chunks + G * p.W * (2ull * p.wpart_slots() + 1) * sizeof(ge_p3) + G + 2 * G +
-               18 * 16 + 4 * G;
+               18 * 16 + 4 * G + 8 * G + 32;
     if (p.merged) b += 32ull * n + 32 * G + max_items(n, p) * 4 * sizeof(fe);
     else b += 16 + 4 * G + (G << p.m_log2) / kSubGroup + 16 + (size_t)n * 32 * sizeof(fe) + 3 * 16 +
               G * 8 * sizeof(fe) + 16 + 4ull * n + 2 * 16 + 4 * G + 2 * 16 + G * 4 * sizeof(fe) + 16;
@@ -241,9 +275,14 @@ struct MsmWork {
     w.join_count = reinterpret_cast<uint32_t *>(b + o); o = up(o + 4 * G);
     w.wpart = reinterpret_cast<ge_p3 *>(b + o); o = up(o + G * p.W * 2ull * p.wpart_slots() * sizeof(ge_p3));
     w.wsum = reinterpret_cast<ge_p3 *>(b + o); o = up(o + G * p.W * sizeof(ge_p3));
+    w.grp_chunks = reinterpret_cast<uint32_t *>(b + o); o = up(o + 4 * G);
+    w.chunk_end = reinterpret_cast<uint32_t *>(b + o); o = up(o + 4 * G);
     w.group_ok = b + o; o = up(o + G);
     w.sort_ovf = b + o; o = up(o + 2 * G);
     w.n_pts = 2 * n;
+    w.merge_pk = nullptr;
+    w.compact = 0;
+    w.ent_total = nullptr;
     w.wscal = w.bscal = nullptr;
     w.item_pt = nullptr;
     w.fail_count = w.fail_list = nullptr;

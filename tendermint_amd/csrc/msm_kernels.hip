@@ -15,7 +15,9 @@
 #include "ktimer.h"
 #include "verify_kernels.h"
 #include "halfscalar.h"
+#include "knobs.h"
 
+#include <algorithm>
 #include <atomic>
 #include <mutex>
 #include <vector>
@@ -162,6 +164,11 @@ __device__ __forceinline__ void p3_add(ge_p3 &a, const ge_p3 &b) {
   ge_p1p1_to_p3(a, r);
 }
 
+// Accumulators k_msm_sort keeps for runs of one key: a run with followers
+// has at least two entries, so m / 2 covers every group of up to 512; larger
+// groups merge their first 256 runs.
+TMV_HD uint32_t merge_runs(const MsmParams &p) { return p.m() / 2 < 256u ? p.m() / 2 : 256u; }
+
 __device__ __forceinline__ void p3_dbl(ge_p3 &a) {
   ge_p1p1 r;
   ge_p3_dbl(r, a);
@@ -169,8 +176,6 @@ __device__ __forceinline__ void p3_dbl(ge_p3 &a) {
 }
 
 }  // namespace
-
-// One workgroup per group of m entries}  // namespace
 
 // One workgroup per group of m entries: z_e, z_e k_e mod l, sum z_e s_e mod l
 // (the B scalar), then a counting sort of the (window, |digit|) bucket entries
@@ -344,6 +349,124 @@ k_msm_sort(const uint8_t *__restrict__ sig, const uint32_t *__restrict__ idx, co
 #pragma unroll
   for (int t = 0; t < 8; t++) bsc[t] = red[t];
 
+  // Runs of one key (msm.h): every live entry whose key encoding equals that
+  // of an earlier live entry of the group adds its z k to that entry's
+  // accumulator and emits no A digits (its wv becomes 0, so both digit passes
+  // below skip it alike); the run's first entry emits the digits of the sum
+  // against its own point.  The tables alias red / scan / the staging area,
+  // which are free between the B scalar above and the scan below.
+  if constexpr (!SR && !KM) {
+    if (mw.merge_pk) {  // block-uniform
+      constexpr uint32_t kNone = 0xffffffffu, kWant = 0xfffffffeu;
+      const uint32_t TS = 2u << p.m_log2, tmask = TS - 1, tshift = 31 - p.m_log2;
+      const uint32_t RUNS = merge_runs(p);
+      uint32_t *ttag = red, *tlead = ttag + TS, *trun = tlead + TS, *nruns = trun + TS, *racc = nruns + 1;
+      __syncthreads();  // every thread has read the B scalar
+      for (uint32_t t = tid; t < TS; t += BS) {
+        ttag[t] = 0;
+        tlead[t] = kNone;
+        trun[t] = kNone;
+      }
+      for (uint32_t t = tid; t < RUNS * 16; t += BS) racc[t] = 0;
+      if (tid == 0) *nruns = 0;
+      __syncthreads();
+      auto key_words = [&](uint32_t kw[8], uint32_t j) {
+        const uint32_t e = e0 + j;
+        const uint32_t i = idx ? idx[e] : e;
+        if (aligned) load_words_aligned(kw, mw.merge_pk + 32ull * i);
+        else load_words_unaligned(kw, mw.merge_pk + 32ull * i);
+      };
+      uint32_t myslot[R];
+      // the table: open addressing on a 32-bit tag of the encoding (never 0);
+      // a slot's leader is the lowest entry index that carries its tag
+#pragma unroll
+      for (int r = 0; r < R; r++) {
+        myslot[r] = 0;
+        if (!live[r]) continue;
+        uint32_t kw[8];
+        key_words(kw, tid + r * BS);
+        uint32_t tag = 0x811c9dc5u;
+#pragma unroll
+        for (int t = 0; t < 8; t++) tag = (tag ^ kw[t]) * 0x01000193u + (tag >> 15);
+        tag |= 1u;
+        uint32_t h = (tag * 0x9e3779b1u) >> tshift;
+        for (;;) {  // at most m live entries in 2m slots: an empty slot exists
+          const uint32_t old = atomicCAS(&ttag[h], 0u, tag);
+          if (old == 0 || old == tag) break;
+          h = (h + 1) & tmask;
+        }
+        atomicMin(&tlead[h], tid + r * BS);
+        myslot[r] = h;
+      }
+      __syncthreads();
+      // followers: same tag as an earlier live entry AND the same 32 bytes
+      bool follower[R], leader[R];
+#pragma unroll
+      for (int r = 0; r < R; r++) {
+        follower[r] = leader[r] = false;
+        if (!live[r]) continue;
+        const uint32_t lead = tlead[myslot[r]];
+        leader[r] = lead == tid + r * BS;
+        if (leader[r]) continue;
+        uint32_t kw[8], lw[8];
+        key_words(kw, tid + r * BS);
+        key_words(lw, lead);
+        uint32_t diff = 0;
+#pragma unroll
+        for (int t = 0; t < 8; t++) diff |= kw[t] ^ lw[t];
+        if (diff) continue;  // another key under the same tag: stays single
+        follower[r] = true;
+        trun[myslot[r]] = kWant;  // (every writer stores the same word)
+      }
+      __syncthreads();
+      // a leader with followers takes an accumulator; past RUNS (cannot
+      // happen while RUNS >= m / 2) its followers stay single
+#pragma unroll
+      for (int r = 0; r < R; r++) {
+        if (!leader[r] || trun[myslot[r]] != kWant) continue;
+        const uint32_t sl = atomicAdd(nruns, 1u);
+        trun[myslot[r]] = sl < RUNS ? sl : kNone;
+      }
+      __syncthreads();
+      // 16-bit limbs in 32-bit words: fewer than 2^10 addends cannot overflow
+#pragma unroll
+      for (int r = 0; r < R; r++) {
+        if (!follower[r]) continue;
+        const uint32_t sl = trun[myslot[r]];
+        if (sl >= RUNS) continue;
+#pragma unroll
+        for (int t = 0; t < 8; t++) {
+          atomicAdd(&racc[sl * 16 + 2 * t], wv[r][t] & 0xffffu);
+          atomicAdd(&racc[sl * 16 + 2 * t + 1], wv[r][t] >> 16);
+          wv[r][t] = 0;
+        }
+      }
+      __syncthreads();
+#pragma unroll
+      for (int r = 0; r < R; r++) {
+        if (!leader[r]) continue;
+        const uint32_t sl = trun[myslot[r]];
+        if (sl >= RUNS) continue;
+        uint32_t x[16];
+        uint64_t c = 0;
+#pragma unroll
+        for (int t = 0; t < 8; t++) {
+          c += (uint64_t)racc[sl * 16 + 2 * t] + (wv[r][t] & 0xffffu);
+          const uint32_t lo16 = (uint32_t)c & 0xffffu;
+          c >>= 16;
+          c += (uint64_t)racc[sl * 16 + 2 * t + 1] + (wv[r][t] >> 16);
+          x[t] = lo16 | (((uint32_t)c & 0xffffu) << 16);
+          c >>= 16;
+        }
+        x[8] = (uint32_t)c;
+#pragma unroll
+        for (int t = 9; t < 16; t++) x[t] = 0;
+        sc_reduce512(wv[r], x);
+      }
+      // (the aliased words are next written after pass 1's barrier)
+    }
+  }
+
   // pass 1: bucket sizes
 #pragma unroll
   for (int r = 0; r < R; r++) {
@@ -378,6 +501,8 @@ k_msm_sort(const uint8_t *__restrict__ sig, const uint32_t *__restrict__ idx, co
   // k_msm_horner / k_loc_search fail it -- never a wrong sum
   const bool ovf = scan[BS] > p.cap;  // block-uniform
   if (tid == 0) mw.sort_ovf[(LOC ? p.groups : 0) + slot] = ovf ? 1 : 0;
+  if (tid == 0 && !ovf && mw.ent_total) atomicAdd(mw.ent_total, (unsigned long long)scan[BS]);
+  if (tid == 0) mw.grp_chunks[slot] = ovf ? 0u : (scan[BS] + p.L - 1) / p.L;  // k_msm_chunk_scan's input
   if (ovf) {
     for (uint32_t t = tid; t < WH; t += BS) {
       mw.bk_start[bbase + t] = gbase;
@@ -458,7 +583,10 @@ k_msm_sort(const uint8_t *__restrict__ sig, const uint32_t *__restrict__ idx, co
       ent_bk[wbeg + i] = st_bk[i];
     }
   }
-  for (uint32_t t = total + tid; t < p.cap; t += BS) ent_bk[t] = kMsmEmpty;
+  // padding: to the end of the group's slots, or, where the accumulation
+  // reads the live chunks only (mw.compact), to the end of the last of them
+  const uint32_t pad_end = mw.compact ? min(p.cap, (total + p.L - 1) / p.L * p.L) : p.cap;
+  for (uint32_t t = total + tid; t < pad_end; t += BS) ent_bk[t] = kMsmEmpty;
 }
 
 #ifdef TMV_CHECKS
@@ -499,11 +627,35 @@ k_msm_accum(const uint32_t *count_ptr, uint32_t n, MsmWork mw, MsmParams p) {
   // (mixed batches size the grid for n but use only their kind's groups)
   const uint32_t cpg = p.chunks_per_group();
   const uint32_t live_groups = (entry_count(count_ptr, n) + p.m() - 1) >> p.m_log2;
-  const uint32_t live_blocks = (live_groups * cpg + blockDim.x - 1) / blockDim.x;
+  if (live_groups == 0) return;
+  // compact launches (mw.chunk_end, k_msm_chunk_scan): lanes cover only the
+  // chunks that hold entries, group after group, so a group that fills a
+  // third of its slots (runs of one key merged, msm.h) does not leave the
+  // rest of its last wave and two dead workgroups behind.  Neighbouring lanes
+  // still hold neighbouring chunks wherever a bucket crosses a chunk edge,
+  // since a bucket never leaves its group.
+  const uint32_t total = mw.chunk_end ? mw.chunk_end[live_groups - 1] : live_groups * cpg;
+  const uint32_t live_blocks = (total + blockDim.x - 1) / blockDim.x;
   const uint32_t per_xcd = (live_blocks + 7) / 8;
   if ((blockIdx.x >> 3) >= per_xcd) return;
   const uint32_t lb = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
-  const uint32_t t = lb * blockDim.x + threadIdx.x;
+  uint32_t t = lb * blockDim.x + threadIdx.x;
+  if (mw.chunk_end) {
+    if (lb * blockDim.x >= total) return;  // block-uniform
+    // the group of the block's first chunk (uniform search), then a few steps per lane
+    uint32_t lo = 0, hi = live_groups - 1;
+    while (lo < hi) {
+      const uint32_t mid = (lo + hi) >> 1;
+      if (mw.chunk_end[mid] > lb * blockDim.x) hi = mid;
+      else lo = mid + 1;
+    }
+    if (t >= total) return;
+    uint32_t gc = lo;
+    while (gc + 1 < live_groups && mw.chunk_end[gc] <= t) gc++;
+    const uint32_t off = t - (gc ? mw.chunk_end[gc - 1] : 0u);
+    if (off >= cpg) return;  // cannot happen: a group's count is at most cap / L
+    t = gc * cpg + off;
+  }
   const uint32_t g = t / cpg;
   if (g >= live_groups) return;
   const uint32_t base = t * L;
@@ -614,6 +766,34 @@ k_msm_accum(const uint32_t *count_ptr, uint32_t n, MsmWork mw, MsmParams p) {
 #ifdef TMV_CHECKS
     if ((int)lane == leader) atomicAdd(&g_joins_named, (uint32_t)__popcll(jm));
 #endif
+  }
+}
+
+// Inclusive prefix of the live groups' chunk counts (k_msm_sort's
+// grp_chunks) for k_msm_accum's compact lane order: one workgroup, a
+// contiguous segment of groups per thread.
+constexpr int kScanBlock = 1024;
+__global__ void __launch_bounds__(kScanBlock)
+k_msm_chunk_scan(const uint32_t *count_ptr, uint32_t n, MsmWork mw, MsmParams p) {
+  __shared__ uint32_t part[kScanBlock];
+  const uint32_t live_groups = (entry_count(count_ptr, n) + p.m() - 1) >> p.m_log2;
+  const uint32_t cpg = p.chunks_per_group();
+  const uint32_t seg = (live_groups + kScanBlock - 1) / kScanBlock;
+  const uint32_t lo = min(live_groups, threadIdx.x * seg), hi = min(live_groups, lo + seg);
+  uint32_t sum = 0;
+  for (uint32_t g = lo; g < hi; g++) sum += min(mw.grp_chunks[g], cpg);
+  part[threadIdx.x] = sum;
+  __syncthreads();
+  for (uint32_t d = 1; d < kScanBlock; d <<= 1) {  // Hillis-Steele inclusive scan
+    const uint32_t v = threadIdx.x >= d ? part[threadIdx.x - d] : 0;
+    __syncthreads();
+    part[threadIdx.x] += v;
+    __syncthreads();
+  }
+  uint32_t run = part[threadIdx.x] - sum;
+  for (uint32_t g = lo; g < hi; g++) {
+    run += min(mw.grp_chunks[g], cpg);
+    mw.chunk_end[g] = run;
   }
 }
 
@@ -1147,8 +1327,12 @@ k_msm_subcheck(const uint8_t *__restrict__ sig, const uint32_t *__restrict__ idx
 
 // Dynamic LDS of k_msm_sort: the bucket counters / cursors, the scalar
 // reduction, the scan, and one window's staged entries (point, bucket).
+// (the run merge's tables alias everything behind the histogram: 3 x 2m
+// table words, a counter, 16 limbs per run)
 static size_t sort_smem(const MsmParams &p, uint32_t bs) {
-  return ((size_t)p.W * p.H + bs * 9 + bs + 1 + 2 * (2 * p.m() + 1)) * sizeof(uint32_t);
+  const size_t sort = bs * 9 + bs + 1 + 2 * (2 * p.m() + 1);
+  const size_t merge = 6 * p.m() + 1 + 16 * merge_runs(p);
+  return ((size_t)p.W * p.H + std::max(sort, merge)) * sizeof(uint32_t);
 }
 
 #ifdef TMV_CHECKS
@@ -1170,6 +1354,14 @@ k_check_buckets(const uint32_t *count_ptr, uint32_t n, MsmWork mw, MsmParams p) 
 }
 #endif
 
+// k_msm_accum runs over the live chunks only (k_msm_chunk_scan) in launches of
+// at least this many groups: kMsmCompactGroups, or the test aid's value
+// (tmv_internal_option "compact_groups"; 0 restores the default), so that
+// tests reach the compact order at small shapes.
+static std::atomic<uint32_t> g_compact_groups{kMsmCompactGroups};
+void set_compact_groups(uint32_t g) { g_compact_groups = g ? g : kMsmCompactGroups; }
+static bool compact_on(const MsmParams &p) { return p.groups >= g_compact_groups.load(std::memory_order_relaxed); }
+
 // Bucket sums, window parts and window sums (shared by both forms).
 // timed: bracket the first two kernels with the live kernel timer (the
 // located fallback's second pass over the failing groups is not timed).
@@ -1181,6 +1373,14 @@ static hipError_t launch_buckets(const uint32_t *count_ptr, uint32_t n, MsmWork 
 #ifdef TMV_CHECKS
   if ((e = hipMemsetAsync(mw.bk_sum, 0, (size_t)p.groups * p.W * p.H * sizeof(ge_p3), stream)) != hipSuccess) return e;
 #endif
+  // launches of many groups run the accumulation over the live chunks only;
+  // small ones keep one lane per slot chunk and skip the scan's launch
+  if (compact_on(p)) {
+    hipLaunchKernelGGL(k_msm_chunk_scan, dim3(1), dim3(kScanBlock), 0, stream, count_ptr, n, mw, p);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  } else {
+    mw.chunk_end = nullptr;
+  }
   void *tk = timed ? ktimer::begin(ktimer::kAccum, stream) : nullptr;
   if (p.L == 16)
     hipLaunchKernelGGL(k_msm_accum<16>, dim3(8 * per_xcd), dim3(256), 0, stream, count_ptr, n, mw, p);
@@ -1267,6 +1467,15 @@ bool locate_enabled(uint32_t n, const MsmParams &p) {
   return lmin && n >= lmin && !p.sub && p.WL() <= p.W;
 }
 
+// Runs of one key in k_msm_sort (msm.h): on unless switched off (test aid
+// tmv_internal_option "key_merge"; A/B knob TMV_KEY_MERGE).
+static std::atomic<int> g_key_merge{1};
+void set_key_merge(int on) { g_key_merge = on ? 1 : 0; }
+static bool key_merge_on() {
+  const char *e = ab_knob("TMV_KEY_MERGE");
+  return e ? atoi(e) != 0 : g_key_merge.load(std::memory_order_relaxed) != 0;
+}
+
 // Views of a launch's work arrays for the entries of groups [g0, ...): the
 // throughput stages of one part of a launch run on these exactly as on
 // a whole batch (indices inside a view are relative), and the whole-launch
@@ -1295,6 +1504,8 @@ static MsmWork msm_view(MsmWork mw, const MsmParams &p, uint32_t n, uint64_t g0)
   mw.part_last += g0 * p.chunks_per_group();
   mw.join_b += g0 * p.chunks_per_group();
   mw.join_count += g0;  // the view's own counter: parts may run at once
+  mw.grp_chunks += g0;
+  mw.chunk_end += g0;
   mw.wpart += g0 * p.W * 2ull * p.P;
   mw.wsum += g0 * p.W;
   mw.group_ok += g0;
@@ -1313,6 +1524,7 @@ template <bool SR, bool LOC>
 static hipError_t launch_sort(const uint8_t *sig, const uint32_t *idx, const uint32_t *count_ptr, uint32_t n,
                               uint32_t e_base, const fe *btab_q, Ed25519Work w, MsmWork mw, const MsmParams &p,
                               const MsmSeed &seed, uint8_t *out, int aligned, hipStream_t stream) {
+  mw.compact = compact_on(p) ? 1 : 0;  // launch_buckets decides the same way
   if (p.m_log2 <= 8)
     hipLaunchKernelGGL((k_msm_sort<SR, false, 64, LOC>), dim3(p.groups), dim3(64), sort_smem(p, 64), stream, sig, idx,
                        count_ptr, n, w, mw, p, seed, btab_q, aligned, nullptr, nullptr, out, e_base);
@@ -1347,9 +1559,9 @@ static hipError_t launch_part(const uint8_t *pk, const uint8_t *sig, const uint8
 // reduce every entry's k for the fallback (k_msm_horner_helped; 125k
 // fallback 273 -> 238 us, profiles/r05/ab_horner_help.txt).
 template <bool SR>
-static hipError_t launch_tail(const uint8_t *sig, const uint32_t *idx, const uint32_t *count_ptr, uint32_t n,
-                              const fe *btab_q, Ed25519Work w, MsmWork mw, const MsmParams &p, const MsmSeed &seed,
-                              uint8_t *out, int aligned, hipStream_t stream) {
+static hipError_t launch_tail_stages(const uint8_t *sig, const uint32_t *idx, const uint32_t *count_ptr, uint32_t n,
+                                     const fe *btab_q, Ed25519Work w, MsmWork mw, const MsmParams &p,
+                                     const MsmSeed &seed, uint8_t *out, int aligned, hipStream_t stream) {
   hipError_t e;
   const bool located = locate_enabled(n, p);
   const bool helped = !located && w.hs_buf;
@@ -1395,6 +1607,28 @@ static hipError_t launch_tail(const uint8_t *sig, const uint32_t *idx, const uin
                                   sub_ok, mw.fail_list, mw.fail_count);
 }
 
+// The launch's failing groups, and with the located pass the groups whose
+// one bad entry it named and the entries left to verify one by one, into the
+// device's counters (mw.ent_total[1..3], tmv_group_fail_stats): one lane, after
+// the tail, only in launches that count (TMV_BATCHOPT_STATS).
+__global__ void k_msm_count_groups(MsmWork mw, int located) {
+  atomicAdd(&mw.ent_total[1], (unsigned long long)*mw.fail_count);
+  if (located) {
+    atomicAdd(&mw.ent_total[2], (unsigned long long)*mw.loc_found);
+    atomicAdd(&mw.ent_total[3], (unsigned long long)*mw.fb_count);
+  }
+}
+
+template <bool SR>
+static hipError_t launch_tail(const uint8_t *sig, const uint32_t *idx, const uint32_t *count_ptr, uint32_t n,
+                              const fe *btab_q, Ed25519Work w, MsmWork mw, const MsmParams &p, const MsmSeed &seed,
+                              uint8_t *out, int aligned, hipStream_t stream) {
+  hipError_t e = launch_tail_stages<SR>(sig, idx, count_ptr, n, btab_q, w, mw, p, seed, out, aligned, stream);
+  if (e != hipSuccess || !mw.ent_total || !mw.fail_count) return e;
+  hipLaunchKernelGGL(k_msm_count_groups, dim3(1), dim3(1), 0, stream, mw, locate_enabled(n, p) ? 1 : 0);
+  return hipGetLastError();
+}
+
 template <bool SR>
 static hipError_t launch_check(const uint8_t *pk, const uint8_t *sig, const uint8_t *msg, const uint32_t *msg_off,
                                const uint32_t *idx, const uint32_t *count_ptr, uint32_t n, const fe *btab_q,
@@ -1403,6 +1637,9 @@ static hipError_t launch_check(const uint8_t *pk, const uint8_t *sig, const uint
   if (n == 0) return hipSuccess;
   const int aligned = ((((uintptr_t)pk) | ((uintptr_t)sig)) & 15) == 0;
   w.niels = mw.pts;
+  // runs of one key: single-kind ed25519 launches (a mixed launch's halves
+  // carry count_ptr)
+  mw.merge_pk = !SR && !count_ptr && key_merge_on() ? pk : nullptr;
   hipError_t e = launch_part<SR>(pk, sig, msg, msg_off, idx, count_ptr, n, 0u, btab_q, prefix, w, mw, p, seed, out,
                                  aligned, stream);
   if (e != hipSuccess) return e;
@@ -1421,6 +1658,7 @@ hipError_t launch_batch_check_part(bool sr, const uint8_t *pk, const uint8_t *si
   pp.groups = ((e1 - e0) + p.m() - 1) >> p.m_log2;
   w.niels = mw.pts;
   const uint64_t E = e0;
+  mw.merge_pk = !sr && key_merge_on() ? pk + 32 * E : nullptr;  // the part's entries are relative
   if (sr)
     return launch_part<true>(pk + 32 * E, sig + 64 * E, msg, msg_off + E, nullptr, nullptr, e1 - e0, e0, btab_q,
                              prefix, work_view(w, E), msm_view(mw, p, n, g0), pp, seed, out ? out + E : nullptr,
@@ -1436,6 +1674,7 @@ hipError_t launch_batch_check_tail(bool sr, const uint8_t *pk, const uint8_t *si
   if (n == 0) return hipSuccess;
   const int aligned = ((((uintptr_t)pk) | ((uintptr_t)sig)) & 15) == 0;
   w.niels = mw.pts;
+  mw.merge_pk = !sr && key_merge_on() ? pk : nullptr;
   if (sr) return launch_tail<true>(sig, nullptr, nullptr, n, btab_q, w, mw, p, seed, out, aligned, stream);
   return launch_tail<false>(sig, nullptr, nullptr, n, btab_q, w, mw, p, seed, out, aligned, stream);
 }
@@ -1546,6 +1785,7 @@ static hipError_t launch_km(const uint8_t *pk, const uint8_t *sig, const uint8_t
   hipError_t e = launch_prep_cached<SR>(pk, sig, msg, msg_off, runs.order, n, prefix, w, aligned, stream);
   if (e != hipSuccess) return e;
   const size_t smem = sort_smem(p, kMsmSortBlock);
+  mw.compact = compact_on(p) ? 1 : 0;
   hipLaunchKernelGGL((k_msm_sort<SR, true>), dim3(p.groups), dim3(kMsmSortBlock), smem, stream, sig, runs.order, nullptr,
                      n, w, mw, p, seed, nullptr, aligned, key_slot, kt.ok, nullptr, 0u);
   if ((e = hipGetLastError()) != hipSuccess) return e;

@@ -38,6 +38,7 @@
 #include "host/wait.h"
 #include "knobs.h"
 #include "ktimer.h"
+#include "colorder.h"
 #include "verify_kernels.h"
 #include "votes.h"
 #include "vote_ext.h"
@@ -253,6 +254,11 @@ struct Device {
   tmv::PointCache pc{nullptr, nullptr, 0, 0};
   uint32_t pc_slots = 0;    // capacity (TMV_POINT_CACHE_SLOTS, rounded); 0 = off
   bool pc_tried = false;    // the allocation was attempted (a failure leaves the path off)
+  // bucket entries k_msm_sort sorted on this device (tmv_bucket_entry_stats;
+  // counted by launches of a context with TMV_BATCHOPT_STATS), allocated at the
+  // first such launch
+  unsigned long long *ent_total = nullptr;
+  bool ent_tried = false;
   DeviceBuf d_valset, h_valset;  // tmv_validator_set_hashes staging
   uint32_t *d_secp_gtab = nullptr;             // secp256k1: j G, j = 1..15, affine (secp256k1.h)
   DeviceBuf d_secp_in, h_secp_in, d_secp_work; // tmv_secp256k1_verify_batch staging and workspace
@@ -615,6 +621,7 @@ struct LaunchOpts {
   tmv::MsmParams p_ed_streamed{};  // ... of a streamed one (mixed_check_streamed)
   tmv::MsmSeed seed[2]{};  // [kind]
   int err = 0;             // < 0: no launch (the weights' key could not be drawn)
+  bool stats = false;      // the context counts (TMV_BATCHOPT_STATS): k_msm_sort adds its bucket entries
 };
 
 // Test aid (tmv_internal_random_fault): the next `count` getrandom calls
@@ -726,6 +733,7 @@ static LaunchOpts make_opts(tmv_ctx *ctx, uint32_t flags, uint32_t n, bool merge
                                                      ctx->msm_sub);
     fixed = ctx->fixed_seed;
     if (fixed) std::memcpy(key, ctx->seed, 32);
+    o.stats = ctx->stats;
   }
   if (!fixed && (o.err = draw_weight_key(key)) != 0) return o;
   const uint64_t ctr = ctx->launches.fetch_add(1);
@@ -921,6 +929,36 @@ static int init_device(Device &d) {
   const char *ps = getenv("TMV_POINT_CACHE_SLOTS");
   d.pc_slots = tmv::pc_round_slots(ps ? strtoull(ps, nullptr, 10) : kPointCacheSlots);
   return 0;
+}
+
+// The device's counters of stats launches (MsmWork::ent_total: bucket entries,
+// failing groups, located groups, entries left one by one; null if it could not be allocated: the
+// launch then counts nothing).  Caller holds d.mu.
+static unsigned long long *entry_counter(Device &d) {
+  if (!d.ent_tried) {
+    d.ent_tried = true;
+    void *p = nullptr;
+    if (hipMalloc(&p, 32) != hipSuccess) {
+      (void)hipGetLastError();
+    } else if (hipMemset(p, 0, 32) != hipSuccess) {  // (not on the caller's stream: the launch path stays asynchronous)
+      (void)hipGetLastError();
+      (void)hipFree(p);
+    } else {
+      d.ent_total = static_cast<unsigned long long *>(p);
+    }
+  }
+  return d.ent_total;
+}
+
+// Tile height of the column order of multi-batch launches (colorder.h):
+// kColumnTile unless the test aid (tmv_internal_option "column_tile", < 0
+// restores the default) or the A/B knob TMV_COLUMN_TILE says otherwise;
+// 0 = batch order.
+static std::atomic<int64_t> g_column_tile{-1};
+static uint32_t column_tile() {
+  const char *e = tmv::ab_knob("TMV_COLUMN_TILE");
+  const int64_t v = e ? strtoll(e, nullptr, 10) : g_column_tile.load(std::memory_order_relaxed);
+  return v < 0 ? tmv::kColumnTile : (uint32_t)std::min<int64_t>(v, tmv::kColumnMaxBatches);
 }
 
 // The device's point cache for a launch on stream s (table null: off).  The
@@ -1204,13 +1242,15 @@ static std::vector<uint32_t> stream_parts(uint32_t n, uint32_t m) {
 // joined back into s by `join` before the tail).
 static int batch_check(Device &d, const LaunchOpts &o, bool sr, const uint8_t *pk, const uint8_t *sig,
                        const uint8_t *msg, const uint32_t *off, uint32_t n, uint8_t *out, hipStream_t s,
-                       const PartFeeder *feed = nullptr, hipStream_t s2 = nullptr, hipEvent_t join = nullptr) {
+                       const PartFeeder *feed = nullptr, hipStream_t s2 = nullptr, hipEvent_t join = nullptr,
+                       const uint32_t *idx = nullptr) {
   int rc;
   Workspace *ws = reserve_work(d, n, false, s, &rc, &o.p);
   if (!ws) return rc;
   tmv::Ed25519Work w = tmv::Ed25519Work::carve(ws->work.ptr, n);
   tmv::MsmWork mw = tmv::MsmWork::carve(ws->msm.ptr, n, o.p);
   if (!sr && n >= tmv::point_cache_min()) w.pc = point_cache_view(d, s);
+  if (o.stats) mw.ent_total = entry_counter(d);
   hipError_t e;
   if (feed) {  // parts as their inputs land, then one tail
     const std::vector<uint32_t> b = stream_parts(n, o.p.m());
@@ -1230,7 +1270,8 @@ static int batch_check(Device &d, const LaunchOpts &o, bool sr, const uint8_t *p
     }
     e = tmv::launch_batch_check_tail(sr, pk, sig, n, d.d_btab_q, w, mw, o.p, o.seed[sr ? 1 : 0], out, s);
   } else {
-    e = tmv::launch_batch_check(sr, pk, sig, msg, off, nullptr, nullptr, n, d.d_btab_q, d.d_prefix, w, mw, o.p,
+    // idx (column order of a multi-batch launch): work slot e is entry idx[e]
+    e = tmv::launch_batch_check(sr, pk, sig, msg, off, idx, nullptr, n, d.d_btab_q, d.d_prefix, w, mw, o.p,
                                 o.seed[sr ? 1 : 0], out, s);
   }
   if (e != hipSuccess) { set_error("batch check launch", e); return TMV_ERR_LAUNCH; }
@@ -1455,8 +1496,9 @@ static int launch_key_merged(Device &d, const LaunchOpts &o, bool sr, const uint
 // Enqueue ed25519 verification of n device-resident entries on stream s.
 // Caller holds d.mu.  Chooses the quad or single-lane kernel.
 static int launch_ed25519(Device &d, const LaunchOpts &o, const uint8_t *pk, const uint8_t *sig, const uint8_t *msg,
-                          const uint32_t *off, uint32_t n, uint8_t *valid, hipStream_t s) {
-  if (o.batch_eq) return batch_check(d, o, false, pk, sig, msg, off, n, valid, s);
+                          const uint32_t *off, uint32_t n, uint8_t *valid, hipStream_t s,
+                          const uint32_t *idx = nullptr) {
+  if (o.batch_eq) return batch_check(d, o, false, pk, sig, msg, off, n, valid, s, nullptr, nullptr, nullptr, idx);
   read_env();
   const bool quad = g_kernel_override == 1 || (g_kernel_override == -1 && n <= kQuadMax);
   hipError_t e;
@@ -1533,6 +1575,23 @@ int tmv_internal_option(const char *name, int64_t value) {
   // cache (0 restores the default), so that tests reach it with small batches
   if (name && !strcmp(name, "point_cache_min")) {
     tmv::set_point_cache_min(value < 0 ? 0u : (uint32_t)value);
+    return 0;
+  }
+  // "column_tile": tile height of multi-batch launches' column order (0 =
+  // batch order, < 0 restores the default); "key_merge": 0 = k_msm_sort
+  // merges no runs of one key
+  if (name && !strcmp(name, "column_tile")) {
+    g_column_tile = value;
+    return 0;
+  }
+  // "compact_groups": group count from which k_msm_accum runs over the live
+  // chunks only (0 restores the default)
+  if (name && !strcmp(name, "compact_groups")) {
+    tmv::set_compact_groups(value < 0 ? 0u : (uint32_t)value);
+    return 0;
+  }
+  if (name && !strcmp(name, "key_merge")) {
+    tmv::set_key_merge(value != 0);
     return 0;
   }
   set_error("unknown internal option");
@@ -1654,6 +1713,7 @@ void tmv_close(tmv_ctx *ctx) {
     if (d->kt.tab) (void)hipFree(d->kt.tab);
     if (d->kt.ok) (void)hipFree(d->kt.ok);
     if (d->pc.table) (void)hipFree(d->pc.table);
+    if (d->ent_total) (void)hipFree(d->ent_total);
     if (d->d_bcomb) (void)hipFree(d->d_bcomb);
     if (d->d_prefix) (void)hipFree(d->d_prefix);
     if (d->d_btab_q) (void)hipFree(d->d_btab_q);
@@ -2395,6 +2455,40 @@ int tmv_point_cache_stats(tmv_ctx *ctx, uint64_t *hits, uint64_t *misses, uint32
   return 0;
 }
 
+int tmv_bucket_entry_stats(tmv_ctx *ctx, uint64_t *entries) {
+  if (!ctx) return TMV_ERR_ARG;
+  uint64_t t = 0;
+  for (auto &d : ctx->devs) {
+    std::lock_guard<std::mutex> lk(d->mu);
+    if (!d->ent_total) continue;
+    unsigned long long v = 0;
+    hipError_t e = hipSetDevice(d->id);
+    if (e == hipSuccess) e = hipMemcpy(&v, d->ent_total, sizeof(v), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) { set_error("bucket entry counter", e); return TMV_ERR_NO_DEVICE; }
+    t += v;
+  }
+  if (entries) *entries = t;
+  return 0;
+}
+
+int tmv_group_fail_stats(tmv_ctx *ctx, uint64_t *groups_failed, uint64_t *groups_located, uint64_t *fallback_entries) {
+  if (!ctx) return TMV_ERR_ARG;
+  uint64_t t[3] = {0, 0, 0};
+  for (auto &d : ctx->devs) {
+    std::lock_guard<std::mutex> lk(d->mu);
+    if (!d->ent_total) continue;
+    unsigned long long v[4] = {0, 0, 0, 0};
+    hipError_t e = hipSetDevice(d->id);
+    if (e == hipSuccess) e = hipMemcpy(v, d->ent_total, sizeof(v), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) { set_error("group counters", e); return TMV_ERR_NO_DEVICE; }
+    for (int k = 0; k < 3; k++) t[k] += v[k + 1];
+  }
+  if (groups_failed) *groups_failed = t[0];
+  if (groups_located) *groups_located = t[1];
+  if (fallback_entries) *fallback_entries = t[2];
+  return 0;
+}
+
 #ifdef TMV_CHECKS
 // Test hooks of the checks build only: read and overwrite the point cache of
 // the context's first device (poisoning tests).  bytes = slots x 64.
@@ -2561,7 +2655,12 @@ int tmv_verify_batches_device(tmv_ctx *ctx, int device, uint8_t key_kind, uint32
   Workspace *ws = reserve_work(*dev, n, false, s, &rc, o.batch_eq ? &o.p : nullptr);
   if (!ws) return rc;
   Layout L(n, (size_t)M);
-  const size_t need = L.total + align16(n);
+  // column order (colorder.h): ed25519 launches of several batches through
+  // the batch equation run their work slots down the columns of tiles of T
+  // batches, so that one validator set's keys form runs inside the groups
+  const uint32_t T = column_tile();
+  const bool columns = key_kind == TMV_KIND_ED25519 && o.batch_eq && n_batches > 1 && T > 0;
+  const size_t need = L.total + align16(n) + (columns ? 4ull * n : 0);
   if (need > ws->gather.cap) {
     if ((e = wait_event(*dev, ws->done)) != hipSuccess) return wait_rc(e);
     if ((e = ws->gather.ensure(need, false)) != hipSuccess) { set_error("hipMalloc(gather)", e); return TMV_ERR_NOMEM; }
@@ -2574,8 +2673,25 @@ int tmv_verify_batches_device(tmv_ctx *ctx, int device, uint8_t key_kind, uint32
       set_error("gather launch", e);
       return TMV_ERR_LAUNCH;
     }
+  uint32_t *idx = nullptr;
+  if (columns) {
+    auto plan = std::make_unique<tmv::ColumnPlan>();
+    uint32_t at = 0;
+    for (uint32_t b = 0; b < n_batches; b++) {
+      plan->start[b] = at;
+      at += batches[b].n;
+    }
+    plan->start[n_batches] = at;
+    plan->K = n_batches;
+    plan->T = T;
+    idx = reinterpret_cast<uint32_t *>(g + L.total + align16(n));
+    if ((e = tmv::launch_column_order(*plan, idx, s)) != hipSuccess) {
+      set_error("column order launch", e);
+      return TMV_ERR_LAUNCH;
+    }
+  }
   if (key_kind == TMV_KIND_ED25519)
-    rc = launch_ed25519(*dev, o, g + L.pk, g + L.sig, g + L.msg, goff, n, reinterpret_cast<uint8_t *>(gst), s);
+    rc = launch_ed25519(*dev, o, g + L.pk, g + L.sig, g + L.msg, goff, n, reinterpret_cast<uint8_t *>(gst), s, idx);
   else
     rc = launch_sr25519(*dev, o, g + L.pk, g + L.sig, g + L.msg, goff, n, gst, s);
   if (rc != 0) return rc;

@@ -146,6 +146,12 @@ bool read_checks(uint32_t out[3], bool reset);
 // Test aid (tmv_internal_option "half_scalars"): 1 = the product's half-size
 // scalars, 0 = every entry on the full-k chain, 2 = every third entry.
 void set_half_scalar_mode(int mode);
+// Test aid (tmv_internal_option "key_merge"): 0 = k_msm_sort merges no runs
+// of one key (msm.h), 1 = the product.
+void set_key_merge(int on);
+// Test aid (tmv_internal_option "compact_groups"): launches of at least this
+// many groups run k_msm_accum over the live chunks only (0 = the default).
+void set_compact_groups(uint32_t groups);
 // Launches of at least this many entries use the located fallback
 // (TMV_LOCATE_MIN, 0 = never).
 uint32_t locate_min_entries();
@@ -201,6 +207,10 @@ struct BatchRefs {
 hipError_t launch_gather(const BatchRefs &r, uint8_t *pk, uint8_t *sig, uint32_t *off, uint8_t *msg,
                          hipStream_t stream);
 hipError_t launch_scatter(const BatchRefs &r, const int8_t *status, hipStream_t stream);
+// Column order of a multi-batch launch (colorder.h): idx[slot] = gathered
+// entry, N words.
+struct ColumnPlan;
+hipError_t launch_column_order(const ColumnPlan &c, uint32_t *idx, hipStream_t stream);
 
 // Key-merged batch equation (msm.h): R decode + challenge with Niels(-R) in
 // w.niels, and the key-cached comb verification of the entries of failing

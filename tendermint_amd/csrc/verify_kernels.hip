@@ -168,7 +168,7 @@ k_prep_fused(const uint8_t *__restrict__ pk, const uint8_t *__restrict__ sig, co
 
 // ---------------------------------------------------------------------------
 // The prep with the point cache (point_cache.h; ed25519 batch-equation
-// launches of contiguous entries).  k_prep_probe is k_prep_fused with the A
+// launches; with idx, work slot e reads entry idx[e] as k_prep_fused does).  k_prep_probe is k_prep_fused with the A
 // lanes replaced by probes: R blocks first (the long chains), then the hash
 // blocks, then the probe blocks.  A probe that passes the checked load writes
 // A's outputs; every other lane appends its entry to the launch's miss list
@@ -177,30 +177,32 @@ k_prep_fused(const uint8_t *__restrict__ pk, const uint8_t *__restrict__ sig, co
 // neighbours walk the square-root chain with it.
 __global__ void __launch_bounds__(kVerifyBlock)
 k_prep_probe(const uint8_t *__restrict__ pk, const uint8_t *__restrict__ sig, const uint8_t *__restrict__ msg,
-             const uint32_t *__restrict__ msg_off, uint32_t n, Ed25519Work w, int aligned, uint32_t rblocks,
-             uint32_t hblocks) {
+             const uint32_t *__restrict__ msg_off, const uint32_t *__restrict__ idx, uint32_t n, Ed25519Work w,
+             int aligned, uint32_t rblocks, uint32_t hblocks) {
   if (blockIdx.x < rblocks) {
     const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= n) return;
+    const uint32_t i = idx ? idx[e] : e;
     uint32_t r_w[8];
-    if (aligned) load_words_aligned(r_w, sig + 64ull * e);
-    else load_words_unaligned(r_w, sig + 64ull * e);
+    if (aligned) load_words_aligned(r_w, sig + 64ull * i);
+    else load_words_unaligned(r_w, sig + 64ull * i);
     ge_p3 P;
     const bool ok = ge_decode_zip215(P, r_w);
     prep_store_point<false>(e, false, ok, P, w);
     return;
   }
   if (blockIdx.x < rblocks + hblocks) {
-    prep_hash_block<false>(blockIdx.x - rblocks, pk, sig, msg, msg_off, nullptr, nullptr, n, w, nullptr, aligned);
+    prep_hash_block<false>(blockIdx.x - rblocks, pk, sig, msg, msg_off, idx, nullptr, n, w, nullptr, aligned);
     return;
   }
   const uint32_t e = (blockIdx.x - rblocks - hblocks) * blockDim.x + threadIdx.x;
   const bool live = e < n;
   bool hit = false;
   if (live) {
+    const uint32_t i = idx ? idx[e] : e;
     uint32_t a_w[8];
-    if (aligned) load_words_aligned(a_w, pk + 32ull * e);
-    else load_words_unaligned(a_w, pk + 32ull * e);
+    if (aligned) load_words_aligned(a_w, pk + 32ull * i);
+    else load_words_unaligned(a_w, pk + 32ull * i);
     ge_p3 P;
     hit = pc_probe(P, w.pc.table, w.pc.bucket_mask, a_w);
     if (hit) prep_store_point<false>(e, true, true, P, w);
@@ -227,16 +229,18 @@ k_prep_probe(const uint8_t *__restrict__ pk, const uint8_t *__restrict__ sig, co
 // (block-uniform, as k_verify_quad_list's exit on fail_count).
 constexpr int kMissBlock = 64;
 __global__ void __launch_bounds__(kMissBlock)
-k_prep_miss(const uint8_t *__restrict__ pk, uint32_t n, Ed25519Work w, int aligned) {
+k_prep_miss(const uint8_t *__restrict__ pk, const uint32_t *__restrict__ idx, uint32_t n, Ed25519Work w,
+            int aligned) {
   const uint32_t cnt = min(*w.miss_count, n);
   if (blockIdx.x * kMissBlock >= cnt) return;  // block-uniform
   const uint32_t t = blockIdx.x * kMissBlock + threadIdx.x;
   if (t >= cnt) return;
   const uint32_t e = w.miss_list[t];
   if (e >= n) return;  // cannot happen (the probe pass lists entries of this launch)
+  const uint32_t i = idx ? idx[e] : e;
   uint32_t a_w[8];
-  if (aligned) load_words_aligned(a_w, pk + 32ull * e);
-  else load_words_unaligned(a_w, pk + 32ull * e);
+  if (aligned) load_words_aligned(a_w, pk + 32ull * i);
+  else load_words_unaligned(a_w, pk + 32ull * i);
   ge_p3 P;
   const bool ok = ge_decode_zip215(P, a_w);
   if (ok) pc_insert(w.pc.table, w.pc.bucket_mask, a_w, P.X);
@@ -1185,20 +1189,21 @@ hipError_t launch_prep(const uint8_t *pk, const uint8_t *sig, const uint8_t *msg
                        Ed25519Work w, int aligned, hipStream_t stream) {
   const uint32_t dblocks = (uint32_t)((2ull * n + kVerifyBlock - 1) / kVerifyBlock);
   const uint32_t hblocks = (n + kVerifyBlock - 1) / kVerifyBlock;
-  // point cache: ed25519 batch-equation launches of contiguous entries
-  const bool cached = !SR && w.niels && !idx && !count_ptr && w.pc.table && w.miss_list && n >= w.pc.min_n;
+  // point cache: ed25519 batch-equation launches whose view carries the
+  // table (contiguous entries, or the column order's index list)
+  const bool cached = !SR && w.niels && !count_ptr && w.pc.table && w.miss_list && n >= w.pc.min_n;
   void *tk = ktimer::begin(ktimer::kPrep, stream);
   hipError_t e;
   if (cached) {
     e = hipMemsetAsync(w.miss_count, 0, sizeof(uint32_t), stream);
     if (e == hipSuccess) {
-      hipLaunchKernelGGL(k_prep_probe, dim3(3 * hblocks), dim3(kVerifyBlock), 0, stream, pk, sig, msg, msg_off, n, w,
-                         aligned, hblocks, hblocks);
+      hipLaunchKernelGGL(k_prep_probe, dim3(3 * hblocks), dim3(kVerifyBlock), 0, stream, pk, sig, msg, msg_off, idx,
+                         n, w, aligned, hblocks, hblocks);
       e = hipGetLastError();
     }
     if (e == hipSuccess) {
-      hipLaunchKernelGGL(k_prep_miss, dim3((n + kMissBlock - 1) / kMissBlock), dim3(kMissBlock), 0, stream, pk, n, w,
-                         aligned);
+      hipLaunchKernelGGL(k_prep_miss, dim3((n + kMissBlock - 1) / kMissBlock), dim3(kMissBlock), 0, stream, pk, idx, n,
+                         w, aligned);
       e = hipGetLastError();
     }
   } else {
