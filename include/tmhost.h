@@ -354,6 +354,78 @@ typedef struct {
 int tmv_proofs_verify(tmv_ctx *ctx, const tmv_proof_in *items, uint32_t n, int32_t *results, char *errs,
                       size_t err_stride);
 
+/* ---- ABCI query proofs and tx proofs (light/rpc/client.go) ----
+ * What the light client's RPC wrapper checks against a trusted header:
+ * ABCIQueryWithOptions (light/rpc/client.go:148-217) runs
+ * merkle.DefaultProofRuntime().VerifyValue / VerifyAbsence against AppHash,
+ * Tx(hash, prove) (client.go:525-543) runs TxProof.Validate(DataHash).
+ * Calls with at least $TMV_DEVICE_PROOF_OPS_MIN ops (tx proofs: items; default
+ * 10,000) whose values and keys (txs) average at most
+ * $TMV_DEVICE_PROOF_OPS_MAX_BYTES bytes per op (default 1044; staging moves a
+ * byte more slowly than the host pool hashes it) go to
+ * the device through tmv_merkle_value_ops / tmv_merkle_verify_proofs, in
+ * windows of 16,384 ops; the others, and every call of a build without the
+ * engine, compute on the host worker pool -- the same verdicts and texts
+ * either way.  Both knobs are read on every call.  Of a call that goes to the
+ * device, an item whose keys hold more than that many bytes per op, or whose
+ * value more than 64 times that, is still hashed on the host: one lane would
+ * hash it alone while its window waits.
+ * Left to the caller, whose Go shim has the reference's own code for them and
+ * none of which is data-parallel: protobuf decoding of ProofOp.Data, the
+ * dispatch on ProofOp.Type ("unrecognized proof type"; only "simple:v" ops
+ * come here) and KeyPathToKeys (proof_key_path.go:87-110). */
+
+/* A decoded "simple:v" ProofOp: pop.Key and ValueOp.Proof. */
+typedef struct {
+  tmv_bytes key;
+  tmv_proof proof;
+} tmv_value_op;
+
+typedef struct {
+  const tmv_value_op *ops;
+  uint32_t n_ops;
+  tmv_bytes root;         /* the expected root (AppHash), any length */
+  const tmv_bytes *keys;  /* KeyPathToKeys(keypath), first path part first */
+  uint32_t n_keys;
+  const tmv_bytes *value; /* NULL: VerifyAbsence (args == nil) */
+} tmv_proof_ops_in;
+
+/* ProofRuntime.Verify (crypto/merkle/proof_op.go:124-130) of n items under the
+ * default runtime: results[i] = 0 ok / 1 error with the reference's text at
+ * errs + i*err_stride, in the reference's order:
+ *   every op's Proof.ValidateBasic first (ProofFromProto, proof.go:133-146):
+ *     "decoding proof: decoding a proof operator: " + its text;
+ *   then per op, for a non-empty op key, "key path has insufficient # of
+ *     parts: expected no more keys but got %+v" / "key mismatch on operation
+ *     #%d: expected %+v but got %+v" (keys print as raw bytes and are consumed
+ *     from the last one backwards), then ValueOp.Run: "expected 1 arg, got 0"
+ *     for an absent value (so absence proofs with ops always end there),
+ *     "leaf hash mismatch: want %X got %X";
+ *   "calculated root hash is invalid: expected %X but got %X" (a nil computed
+ *     root prints as nothing and, as in bytes.Equal, equals an empty root);
+ *   "keypath not consumed all".
+ * An item without ops compares its value with the root; without ops and
+ * without a value the reference panics: TMV_ERR_ARG.  Returns the number of
+ * failed items or < 0. */
+int tmv_proof_ops_verify(tmv_ctx *ctx, const tmv_proof_ops_in *items, uint32_t n, int32_t *results, char *errs,
+                         size_t err_stride);
+
+/* types.TxProof with the header's DataHash it is validated against. */
+typedef struct {
+  tmv_bytes root_hash, data; /* TxProof.RootHash, TxProof.Data */
+  tmv_proof proof;           /* TxProof.Proof */
+  tmv_bytes data_hash;       /* Header.DataHash */
+} tmv_tx_proof_in;
+
+/* TxProof.Validate (types/tx.go:286-301) of n items, in its order: "proof
+ * matches different data hash", "proof index cannot be negative", "proof
+ * total must be positive" (Total <= 0), and any failure of
+ * Proof.Verify(RootHash, SHA-256(Data)) as "proof is not internally
+ * consistent".  No ValidateBasic runs: a leaf hash or aunt of another size is
+ * hashed as innerHash would.  Results, texts and return value as above. */
+int tmv_tx_proofs_validate(tmv_ctx *ctx, const tmv_tx_proof_in *items, uint32_t n, int32_t *results, char *errs,
+                           size_t err_stride);
+
 /* ---- blocks (types/block.go) ---- */
 /* Calls that hash at least $TMV_DEVICE_BLOCK_MIN commits (default 32, the rule
  * of tmv_header_hashes) go to the device through

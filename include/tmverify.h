@@ -299,6 +299,44 @@ int tmv_merkle_verify_proofs(tmv_ctx *ctx, uint32_t flags, uint32_t n, const int
                              const uint8_t *root, const uint8_t *data, const uint32_t *leaf_off, int8_t *status_out,
                              uint8_t *leaf_hash_calc, uint8_t *root_calc, uint8_t *root_nil);
 
+/* Chained value proof operators: ValueOp.Run (crypto/merkle/proof_value.go:
+ * 77-98) as ProofOperators.Verify chains it (proof_op.go:39-69), for n_items
+ * items in one call -- the merkle work of the light client's
+ * ABCIQueryWithOptions (light/rpc/client.go:148-217).  Item i has the input
+ * value value[value_off[i], value_off[i+1]) (any length, 0 allowed) and owns
+ * the ops [op_off[i], op_off[i+1]), at least one.  Op j, over all
+ * n_ops = op_off[n_items]: the key key[key_off[j], key_off[j+1]) (any length),
+ * total[j], index[j], leaf_hash + 32*j and the aunts
+ * aunts[32*aunt_off[j] .. 32*aunt_off[j+1]), as tmv_merkle_verify_proofs takes
+ * them.  With v the item's value for its first op and the root of the op
+ * before for the others (the empty string when that root is nil: the
+ * reference passes the nil slice on and hashes it),
+ *   kv      = SHA-256(0x00 || uvarint(len key) || key || 0x20 || SHA-256(v))
+ *   leaf_ok = (kv == leaf_hash)
+ *   root    = computeHashFromAunts(index, total, leaf_hash, aunts)
+ * (proof.go:151-181; from the *given* leaf hash, as the reference does; nil
+ * exactly when tmv_merkle_verify_proofs says nil, so total < 0 and index < 0
+ * are no errors here).  An item does not stop at a mismatch.
+ * Outputs, any of them NULL to skip.  Per item: value_digest n_items x 32
+ * (SHA-256(value)); status_out 0 ok, 3 some op's leaf hash differs, 4 the last
+ * op's root is nil or differs from root + 32*i (the numbers of
+ * tmv_merkle_verify_proofs); fail_op_out the first op with a mismatch, counted
+ * from the item's first op (the last op for status 4, 0 for status 0).  Per
+ * op: kv_hash_calc n_ops x 32, leaf_ok n_ops, root_calc n_ops x 32 (zeros when
+ * nil), root_nil n_ops.
+ * flags: 0, or TMV_MERKLE_LPW(8|16|32|64) to fix the leaves per wave of the
+ * value digests (k_merkle_leaves_long's digest-only form; a tuning aid).
+ * TMV_ERR_ARG: null inputs, offsets that do not start at 0 or decrease, an
+ * item without ops, n_items or n_ops > 2^26, more than 2^30 bytes of values or
+ * of keys, more than 2^28 aunts.  Synchronous, device 0.  Returns 0 (every
+ * status 0), 1 (some not) or < 0. */
+int tmv_merkle_value_ops(tmv_ctx *ctx, uint32_t flags, uint32_t n_items, const uint8_t *value,
+                         const uint32_t *value_off, const uint32_t *op_off, const uint8_t *key, const uint32_t *key_off,
+                         const int64_t *total, const int64_t *index, const uint8_t *leaf_hash, const uint8_t *aunts,
+                         const uint32_t *aunt_off, const uint8_t *root, uint8_t *value_digest, uint8_t *kv_hash_calc,
+                         uint8_t *leaf_ok, uint8_t *root_calc, uint8_t *root_nil, int8_t *status_out,
+                         int32_t *fail_op_out);
+
 /* Sub-groups of failing groups checked / failed (k_msm_subcheck: a failing
  * group's sub-groups of 8 entries are re-checked with the same equation
  * before entry-by-entry verification; TMV_BATCHOPT_STATS; 0 with
@@ -316,7 +354,8 @@ int tmv_verify_mixed_batch_ex(tmv_ctx *ctx, uint32_t flags, const uint8_t *kind,
  * challenge), "k_secp_prep" and "k_secp_verify" (secp256k1), "k_secp_key_table", "k_secp_prep_cached" and
  * "k_secp_verify_comb" (secp256k1 with TMV_FLAG_KEY_CACHE), "k_merkle_leaves_long",
  * "k_merkle_leaves", "k_merkle_tree_levels", "k_merkle_aunts" and "k_merkle_verify_proofs" (the launches
- * of tmv_merkle_proofs / tmv_merkle_verify_proofs), "k_commit_leaves" (tmv_commit_hashes) -- is bracketed by HIP timing events on the stream it runs on
+ * of tmv_merkle_proofs / tmv_merkle_verify_proofs), "k_merkle_digests_long" and "k_merkle_value_ops"
+ * (tmv_merkle_value_ops), "k_commit_leaves" (tmv_commit_hashes) -- is bracketed by HIP timing events on the stream it runs on
  * (process-wide, two event records per launch); 0 turns it off.
  * tmv_kernel_timing_read waits for the recorded launches of `kernel`, returns
  * their summed duration and count, and forgets them.  No reference

@@ -61,13 +61,15 @@ EXPORTS = [
     "tmv_verify_mixed_batch_ex", "tmv_verify_batch_device_ex", "tmv_verify_batches_device",
     "tmv_verify_votes", "tmv_vote_sign_bytes_device", "tmv_verify_votes_and_extensions",
     "tmv_vote_extension_sign_bytes_device", "tmv_merkle_roots",
-    "tmv_merkle_aunt_offsets", "tmv_merkle_proofs", "tmv_merkle_verify_proofs", "tmv_commit_hashes",
+    "tmv_merkle_aunt_offsets", "tmv_merkle_proofs", "tmv_merkle_verify_proofs", "tmv_merkle_value_ops",
+    "tmv_commit_hashes",
     "tmv_kernel_timing", "tmv_kernel_timing_read", "tmv_metrics_read", "tmv_metrics_reset",
     # include/tmhost.h
     "tmv_batch_new", "tmv_batch_add", "tmv_batch_len", "tmv_batch_verify", "tmv_batch_free",
     "tmv_vote_sign_bytes", "tmv_vote_template_encode", "tmv_verify_commit", "tmv_verify_commits",
     "tmv_header_hashes", "tmv_light_verify_many", "tmv_light_verify", "tmv_verify_vote_batch",
     "tmv_part_set_headers", "tmv_part_set_proofs", "tmv_parts_verify", "tmv_proofs_verify",
+    "tmv_proof_ops_verify", "tmv_tx_proofs_validate",
     "tmv_commit_hash_many", "tmv_blocks_validate_basic",
     "tmv_vote_extension_sign_bytes", "tmv_vote_extension_template_encode", "tmv_verify_extended_votes",
 ]
@@ -208,6 +210,9 @@ def lib() -> ctypes.CDLL:
         i64p = ctypes.POINTER(ctypes.c_int64)
         L.tmv_merkle_verify_proofs.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, i64p, i64p, u8p, u8p, u32p, u8p,
                                                u8p, u32p, i8p, u8p, u8p, u8p]
+        L.tmv_merkle_value_ops.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, u8p, u32p, u32p, u8p, u32p, i64p, i64p,
+                                           u8p, u8p, u32p, u8p, u8p, u8p, u8p, u8p, u8p, i8p,
+                                           ctypes.POINTER(ctypes.c_int32)]
         L.tmv_verify_batch_device_ex.argtypes = [vp, ctypes.c_int, ctypes.c_uint8, ctypes.c_uint32, vp, vp, vp, vp,
                                                  vp, ctypes.c_uint32, vp, vp]
         L.tmv_verify_batches_device.argtypes = [vp, ctypes.c_int, ctypes.c_uint8, ctypes.c_uint32,
@@ -619,6 +624,51 @@ class Context:
             _p(aunt_off, ctypes.c_uint32), _p(root), dp, lp, _p(status, ctypes.c_int8), _p(lcalc), _p(rcalc),
             _p(nil)), "tmv_merkle_verify_proofs")
         return rc == 0, status[:n], lcalc[:n], rcalc[:n], nil[:n]
+
+    def merkle_value_ops(self, value, value_off, op_off, key, key_off, total, index, leaf_hash, aunts, aunt_off, root,
+                         flags: int = 0, skip=()):
+        """ValueOp.Run chained per item as ProofOperators.Verify chains it (tmv_merkle_value_ops):
+        (all ok, dict of value_digest (n_items, 32), kv_hash_calc (n_ops, 32), leaf_ok (n_ops,),
+        root_calc (n_ops, 32), root_nil (n_ops,), status (n_items,) int8, fail_op (n_items,) int32).
+        value / key / aunts: uint8 arrays, or None for a null pointer; skip: names of outputs to pass
+        as NULL (they come back as None)."""
+        value_off = np.ascontiguousarray(value_off, np.uint32)
+        op_off = np.ascontiguousarray(op_off, np.uint32)
+        key_off = np.ascontiguousarray(key_off, np.uint32)
+        aunt_off = np.ascontiguousarray(aunt_off, np.uint32)
+        n_items, n_ops = len(op_off) - 1, len(key_off) - 1
+
+        def data(a, width=1):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, np.uint8)
+            return a if a.size else np.zeros(width, np.uint8)
+
+        value, key, aunts = data(value), data(key), data(aunts, 32)
+        leaf_hash, root = data(leaf_hash, 32), data(root, 32)
+        total = np.ascontiguousarray(total, np.int64) if n_ops else np.zeros(1, np.int64)
+        index = np.ascontiguousarray(index, np.int64) if n_ops else np.zeros(1, np.int64)
+        out = {"value_digest": np.zeros((max(n_items, 1), 32), np.uint8),
+               "kv_hash_calc": np.zeros((max(n_ops, 1), 32), np.uint8),
+               "leaf_ok": np.zeros(max(n_ops, 1), np.uint8),
+               "root_calc": np.zeros((max(n_ops, 1), 32), np.uint8),
+               "root_nil": np.zeros(max(n_ops, 1), np.uint8),
+               "status": np.zeros(max(n_items, 1), np.int8),
+               "fail_op": np.zeros(max(n_items, 1), np.int32)}
+        types = {"status": ctypes.c_int8, "fail_op": ctypes.c_int32}
+        ptr = {k: (None if k in skip else _p(v, types.get(k, ctypes.c_uint8))) for k, v in out.items()}
+
+        def opt(a):
+            return None if a is None else _p(a)
+
+        rc = self._check(self._lib.tmv_merkle_value_ops(
+            self._h, flags, n_items, opt(value), _p(value_off, ctypes.c_uint32), _p(op_off, ctypes.c_uint32), opt(key),
+            _p(key_off, ctypes.c_uint32), _p(total, ctypes.c_int64), _p(index, ctypes.c_int64), opt(leaf_hash),
+            opt(aunts), _p(aunt_off, ctypes.c_uint32), opt(root), ptr["value_digest"], ptr["kv_hash_calc"],
+            ptr["leaf_ok"], ptr["root_calc"], ptr["root_nil"], ptr["status"], ptr["fail_op"]),
+            "tmv_merkle_value_ops")
+        size = {"value_digest": n_items, "status": n_items, "fail_op": n_items}
+        return rc == 0, {k: (None if k in skip else v[:size.get(k, n_ops)]) for k, v in out.items()}
 
     def batch_stats(self):
         g, f = ctypes.c_uint64(), ctypes.c_uint64()

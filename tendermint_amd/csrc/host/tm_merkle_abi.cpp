@@ -24,6 +24,7 @@
 #include "merkle_plan.h"
 #include "tm_host_internal.h"
 #include "tm_light.h"
+#include "tm_proof_common.h"
 
 extern "C" int tmv_merkle_proofs(tmv_ctx *ctx, uint32_t flags, const uint8_t *data, const uint32_t *leaf_off,
                                  uint32_t n_leaves, const uint32_t *tree_off, uint32_t n_trees, uint8_t *root_out,
@@ -40,6 +41,11 @@ namespace {
 using tmh::Bytes;
 using tmh::Digest;
 using tmh_internal::parallel_for;
+using tmh_proof::digest_out;
+using tmh_proof::hex_upper;
+using tmh_proof::put;
+using tmh_proof::root_from_aunts;
+using tmh_proof::validate_basic;
 
 constexpr uint64_t kEngineMaxBytes = 1ull << 30;  // tmv_merkle_proofs' limits per call
 constexpr uint64_t kEngineMaxLeaves = 1ull << 26;
@@ -79,49 +85,11 @@ struct Concat {
   }
 };
 
-void put(char *errs, size_t stride, size_t i, const std::string &s) {
-  if (!errs || !stride) return;
-  char *o = errs + i * stride;
-  const size_t m = std::min(s.size(), stride - 1);
-  std::memcpy(o, s.data(), m);
-  o[m] = 0;
-}
-
-std::string hex_upper(const uint8_t *p, size_t n) {
-  static const char d[] = "0123456789ABCDEF";
-  std::string s(2 * n, '0');
-  for (size_t i = 0; i < n; i++) {
-    s[2 * i] = d[p[i] >> 4];
-    s[2 * i + 1] = d[p[i] & 15];
-  }
-  return s;
-}
-
-void digest_out(const Digest &dg, uint8_t out[32]) {
-  for (int i = 0; i < 8; i++)
-    for (int b = 0; b < 4; b++) out[4 * i + b] = (uint8_t)(dg.w[i] >> (24 - 8 * b));
-}
-
 Digest leaf_digest(const uint8_t *p, size_t n) {  // leafHash (crypto/merkle/hash.go)
   static const uint8_t zero = 0;
   Digest dg;
   tmh::Sha256Bytes(dg.w, &zero, 1, p, n);
   return dg;
-}
-
-// innerHash over byte strings of any length (computeHashFromAunts does not
-// look at its aunts' sizes)
-Bytes inner_bytes(const Bytes &l, const Bytes &r) {
-  Bytes buf;
-  buf.reserve(1 + l.size() + r.size());
-  buf.push_back(1);
-  buf.insert(buf.end(), l.begin(), l.end());
-  buf.insert(buf.end(), r.begin(), r.end());
-  Digest dg;
-  tmh::Sha256Bytes(dg.w, nullptr, 0, buf.data(), buf.size());
-  Bytes out(32);
-  digest_out(dg, out.data());
-  return out;
 }
 
 // The tree over n >= 1 leaf digests, every level kept (the pairing of
@@ -167,32 +135,6 @@ bool simple(const Item &it) {  // fits the engine's fixed 32-byte layout
   for (uint32_t a = 0; a < it.pr->n_aunts; a++)
     if (it.pr->aunts[a].len != 32) return false;
   return true;
-}
-
-// computeHashFromAunts (proof.go:151-181), iteratively: the path from
-// (index, total) down by split points, then the aunts folded upwards.
-Bytes root_from_aunts(const tmv_proof &p) {
-  if (!(p.index >= 0 && p.index < p.total)) return {};
-  uint64_t t = (uint64_t)p.total, x = (uint64_t)p.index, mask = 0;
-  uint32_t depth = 0;
-  while (t > 1) {
-    const uint64_t k = tmh::merkle_split_point(t);
-    if (x < k) {
-      t = k;
-    } else {
-      mask |= 1ull << depth;
-      x -= k;
-      t -= k;
-    }
-    depth++;
-  }
-  if (depth != p.n_aunts) return {};
-  Bytes h(p.leaf_hash.p, p.leaf_hash.p + p.leaf_hash.len);
-  for (uint32_t j = 0; j < depth; j++) {
-    const Bytes a(p.aunts[j].p, p.aunts[j].p + p.aunts[j].len);
-    h = ((mask >> (depth - 1 - j)) & 1) ? inner_bytes(a, h) : inner_bytes(h, a);
-  }
-  return h;
 }
 
 void verify_host(const Item &it, Verdict &v) {
@@ -382,26 +324,6 @@ int part_sets(tmv_ctx *ctx, const tmv_bytes *blocks, uint32_t n, uint32_t part_s
     b0 = b1;
   }
   return 0;
-}
-
-std::string validate_basic(const tmv_proof &p) {  // proof.go:98-117
-  char buf[96];
-  if (p.total < 0) return "negative Total";
-  if (p.index < 0) return "negative Index";
-  if (p.leaf_hash.len != 32) {
-    std::snprintf(buf, sizeof buf, "expected LeafHash size to be 32, got %u", p.leaf_hash.len);
-    return buf;
-  }
-  if (p.n_aunts > 100) {  // MaxAunts, proof.go:19
-    std::snprintf(buf, sizeof buf, "expected no more than 100 aunts, got %u", p.n_aunts);
-    return buf;
-  }
-  for (uint32_t i = 0; i < p.n_aunts; i++)
-    if (p.aunts[i].len != 32) {
-      std::snprintf(buf, sizeof buf, "expected Aunts#%u size to be 32, got %u", i, p.aunts[i].len);
-      return buf;
-    }
-  return "";
 }
 
 }  // namespace

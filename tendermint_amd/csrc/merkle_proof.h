@@ -19,6 +19,12 @@ constexpr uint32_t kMerkleLevelSlack = tmh::kMerkleLevelSlack;
 hipError_t launch_merkle_leaves_long(const uint8_t *data, const uint32_t *leaf_off, uint32_t n_leaves, bool prehash,
                                      uint32_t lpw, uint32_t *node, hipStream_t stream);
 
+// SHA-256(item) of items data[leaf_off[i], leaf_off[i+1]) into node (8 state
+// words per item): k_merkle_leaves_long without prefix or second hash; data
+// and lpw as above.
+hipError_t launch_merkle_digests_long(const uint8_t *data, const uint32_t *leaf_off, uint32_t n_items, uint32_t lpw,
+                                      uint32_t *node, hipStream_t stream);
+
 // Trees over the leaf hashes leafn with every level kept in arena
 // (tmh::merkle_arena_nodes(n_leaves, n_trees) x 8 words), then per leaf its
 // serialised hash and, unless aunts_out is null, its aunts at aunt_off.

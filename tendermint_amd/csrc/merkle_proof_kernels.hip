@@ -25,6 +25,9 @@
 //                          Leaves of different lengths differ only in their
 //                          trip counts.  kPrehash: SHA-256(0x00 ||
 //                          SHA-256(item)), the leaf of Txs.Hash.
+//   k_merkle_digests_long  the same kernel body without prefix or second
+//                          hash: SHA-256(item), the value digests of
+//                          tmv_merkle_value_ops (merkle_ops_kernels.hip).
 //   k_merkle_tree_levels   k_merkle_tree's pairing and odd promotion (equal to
 //                          the split-point tree by TestHashAlternatives), one
 //                          workgroup per tree, but every level is kept: level 0
@@ -198,6 +201,101 @@ k_merkle_leaves_long(const uint8_t *data, const uint32_t *__restrict__ leaf_off,
   store_node(node + 8ull * i, st);
 }
 
+// k_merkle_leaves_long without prefix and without kPrehash's second hash: the
+// state words of SHA-256(item).  A kernel of its own, restated line by line:
+// as a third mode of the template it moved k_merkle_leaves_long<false>'s
+// register count.  Same staging, LDS and launch shape.
+__global__ void __launch_bounds__(64)
+k_merkle_digests_long(const uint8_t *data, const uint32_t *__restrict__ leaf_off, uint32_t n_leaves, uint32_t lpw,
+                      uint32_t *__restrict__ node) {
+  extern __shared__ uint4 lds[];
+  int32_t *s_u0 = reinterpret_cast<int32_t *>(lds + lpw * kSlotUnits);
+  uint32_t *s_nu = reinterpret_cast<uint32_t *>(s_u0 + lpw);
+  const uint4 *du = reinterpret_cast<const uint4 *>(data);
+  const uint32_t lane = threadIdx.x;
+  const uint64_t i = (uint64_t)blockIdx.x * lpw + lane;
+  const bool active = lane < lpw && i < n_leaves;
+  constexpr uint32_t pre = 0;  // no prefix
+  // The message is the byte stream that starts `pre` bytes before the leaf
+  // (that byte is overwritten by the prefix): unit u0, shift sh inside it.
+  uint32_t total = 0, nblk = 0, nu = 0, sh = 0;
+  int32_t u0 = 0;
+  if (active) {
+    const uint32_t b = leaf_off[i], len = leaf_off[i + 1] - b;
+    const int64_t p = (int64_t)b - pre;
+    u0 = (int32_t)(p >> 4);
+    sh = (uint32_t)(p & 15);
+    total = len + pre;
+    nblk = (total + 72) / 64;  // room for 0x80 and the 8-byte length
+    nu = len ? (uint32_t)((int32_t)(((uint64_t)b + len - 1) >> 4) - u0) + 1 : 0;  // through the last byte's unit
+  }
+  if (lane < lpw) {
+    s_u0[lane] = u0;
+    s_nu[lane] = nu;
+    if (nu) lds[lane * kSlotUnits] = du[u0];
+  }
+  __syncthreads();
+  const uint32_t nch = (nblk + 7) / 8;
+  const uint32_t ds = sh >> 2;
+  const uint32_t sel = 0x00010203u + (sh & 3) * 0x01010101u;  // v_perm_b32: bytes sh&3 .. of a dword pair, first byte on top
+  const uint64_t bits = (uint64_t)total * 8;
+  const uint4 *slot = lds + lane * kSlotUnits;
+  uint32_t st[8];
+  sha256_init(st);
+  for (uint32_t c = 0; __ballot(c < nch) != 0; c++) {
+    // units 32c + 1 .. 32c + 32 of every leaf of the wave: a half-wave per leaf
+    const uint32_t hl = lane & 31, u = kSegUnits * c + 1 + hl;
+#pragma unroll 4
+    for (uint32_t s2 = 0; s2 < lpw; s2 += 2) {
+      const uint32_t sl = s2 + (lane >> 5);
+      if (sl < lpw && u < s_nu[sl]) lds[sl * kSlotUnits + 1 + hl] = du[(int64_t)s_u0[sl] + u];
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (uint32_t j = 0; j < 8; j++) {
+      const uint32_t blk = 8 * c + j;
+      if (blk >= nblk) break;
+      uint32_t d[20];
+#pragma unroll
+      for (int q = 0; q < 5; q++) {
+        const uint4 v = slot[4 * j + q];
+        d[4 * q] = v.x; d[4 * q + 1] = v.y; d[4 * q + 2] = v.z; d[4 * q + 3] = v.w;
+      }
+      if (ds & 1) {
+#pragma unroll
+        for (int q = 0; q < 19; q++) d[q] = d[q + 1];
+      }
+      if (ds & 2) {
+#pragma unroll
+        for (int q = 0; q < 17; q++) d[q] = d[q + 2];
+      }
+      uint32_t w[16];
+#pragma unroll
+      for (int q = 0; q < 16; q++) w[q] = __builtin_amdgcn_perm(d[q + 1], d[q], sel);
+      if (64 * (blk + 1) > total) {  // the message ends in or before this block
+#pragma unroll
+        for (int q = 0; q < 16; q++) {
+          const int rem = (int)total - (int)(64 * blk + 4 * q);  // message bytes from this word on
+          if (rem <= 0) {
+            w[q] = rem == 0 ? 0x80000000u : 0u;
+          } else if (rem < 4) {
+            w[q] = (w[q] & (0xffffffffu << (32 - 8 * rem))) | (0x80u << (24 - 8 * rem));
+          }
+        }
+        if (blk + 1 == nblk) {
+          w[14] = (uint32_t)(bits >> 32);
+          w[15] = (uint32_t)bits;
+        }
+      }
+      sha256_compress(st, w);
+    }
+    if (lane < lpw) lds[lane * kSlotUnits] = slot[kSegUnits];  // the spill unit opens the next round
+    __syncthreads();
+  }
+  if (!active) return;
+  store_node(node + 8ull * i, st);
+}
+
 template <int kTreeBlock>
 __global__ void __launch_bounds__(kTreeBlock)
 k_merkle_tree_levels(const uint32_t *__restrict__ tree_off, uint32_t n_trees, const uint32_t *leafn, uint32_t *arena,
@@ -354,6 +452,18 @@ hipError_t launch_merkle_leaves_long(const uint8_t *data, const uint32_t *leaf_o
   else
     hipLaunchKernelGGL(k_merkle_leaves_long<false>, grid, block, lds_bytes, stream, data, leaf_off, n_leaves, lpw,
                        node);
+  ktimer::end(tok, stream);
+  return hipGetLastError();
+}
+
+hipError_t launch_merkle_digests_long(const uint8_t *data, const uint32_t *leaf_off, uint32_t n_items, uint32_t lpw,
+                                      uint32_t *node, hipStream_t stream) {
+  if (!n_items) return hipSuccess;
+  if (lpw != 8 && lpw != 16 && lpw != 32 && lpw != 64) return hipErrorInvalidValue;
+  const size_t lds_bytes = (size_t)lpw * (16 * kSlotUnits + 8);
+  void *tok = ktimer::begin(ktimer::kMerkleDigestsLong, stream);
+  hipLaunchKernelGGL(k_merkle_digests_long, dim3((n_items + lpw - 1) / lpw), dim3(64), lds_bytes, stream, data,
+                     leaf_off, n_items, lpw, node);
   ktimer::end(tok, stream);
   return hipGetLastError();
 }

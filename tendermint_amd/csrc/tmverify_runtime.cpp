@@ -1545,6 +1545,8 @@ int tmv_kernel_timing_read(tmv_ctx *ctx, const char *kernel, double *total_ms, u
   else if (!strcmp(kernel, "k_merkle_leaves")) k = tmv::ktimer::kMerkleLeaves;
   else if (!strcmp(kernel, "k_commit_leaves")) k = tmv::ktimer::kCommitLeaves;
   else if (!strcmp(kernel, "k_vote_ext_signbytes")) k = tmv::ktimer::kVoteExtSignbytes;
+  else if (!strcmp(kernel, "k_merkle_digests_long")) k = tmv::ktimer::kMerkleDigestsLong;
+  else if (!strcmp(kernel, "k_merkle_value_ops")) k = tmv::ktimer::kMerkleValueOps;
   else { set_error("unknown timed kernel"); return TMV_ERR_ARG; }
   *total_ms = 0;
   *launches = 0;
@@ -3124,6 +3126,7 @@ int tmv_ed25519_verify_batch_device(tmv_ctx *ctx, int device, const uint8_t *d_p
 
 // tmv_merkle_proofs, tmv_merkle_verify_proofs, tmv_merkle_aunt_offsets
 #include "merkle_runtime.h"
+#include "merkle_ops_runtime.h"
 
 // tmv_commit_hashes
 #include "commit_runtime.h"

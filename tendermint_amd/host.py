@@ -1015,6 +1015,132 @@ def proofs_verify(ctx, items: List[Tuple[Proof, bytes, bytes]], lib=None) -> Lis
     return _texts(results, errs, n)
 
 
+# ---------------------------------------------------------------- ABCI query proofs and tx proofs
+# tmv_proof_ops_verify / tmv_tx_proofs_validate (include/tmhost.h): ProofRuntime.Verify under the default
+# runtime (crypto/merkle/proof_op.go:35-69,114-130, proof_value.go:77-98) and TxProof.Validate
+# (types/tx.go:286-301), what light/rpc/client.go checks against a trusted header.
+
+@dataclass
+class ValueOp:
+    """A decoded "simple:v" ProofOp: pop.Key and ValueOp.Proof."""
+    key: bytes
+    proof: Proof
+
+
+@dataclass
+class ProofOpsItem:
+    """One ProofRuntime.Verify call: keys = KeyPathToKeys(keypath), value None = VerifyAbsence."""
+    ops: List[ValueOp]
+    root: bytes
+    keys: List[bytes]
+    value: Optional[bytes]
+
+
+@dataclass
+class TxProof:
+    """types.TxProof with the Header.DataHash it is validated against."""
+    root_hash: bytes
+    data: bytes
+    proof: Proof
+    data_hash: bytes
+
+
+class CValueOp(ctypes.Structure):
+    _fields_ = [("key", CBytes), ("proof", CProof)]
+
+
+class CProofOpsIn(ctypes.Structure):
+    _fields_ = [("ops", ctypes.POINTER(CValueOp)), ("n_ops", ctypes.c_uint32), ("root", CBytes),
+                ("keys", ctypes.POINTER(CBytes)), ("n_keys", ctypes.c_uint32), ("value", ctypes.POINTER(CBytes))]
+
+
+class CTxProofIn(ctypes.Structure):
+    _fields_ = [("root_hash", CBytes), ("data", CBytes), ("proof", CProof), ("data_hash", CBytes)]
+
+
+def _setup_proof_ops(L):
+    if not getattr(L, "_tmhost_proof_ops", False):
+        L.tmv_proof_ops_verify.argtypes = [ctypes.c_void_p, ctypes.POINTER(CProofOpsIn), ctypes.c_uint32,
+                                           ctypes.POINTER(ctypes.c_int32), ctypes.c_char_p, ctypes.c_size_t]
+        L.tmv_tx_proofs_validate.argtypes = [ctypes.c_void_p, ctypes.POINTER(CTxProofIn), ctypes.c_uint32,
+                                             ctypes.POINTER(ctypes.c_int32), ctypes.c_char_p, ctypes.c_size_t]
+        L._tmhost_proof_ops = True
+    return L
+
+
+class PreparedProofOps:
+    """The C arrays of a tmv_proof_ops_verify call, built once (tools time the call alone)."""
+
+    def __init__(self, items: List[ProofOpsItem]):
+        self.k = k = _Keep()
+        self.n = n = len(items)
+        self.arr = (CProofOpsIn * max(1, n))()
+        for i, it in enumerate(items):
+            ops = (CValueOp * max(1, len(it.ops)))()
+            for j, op in enumerate(it.ops):
+                ops[j] = CValueOp(_ref_bytes(k, op.key), _c_proof(k, op.proof))
+            keys = (CBytes * max(1, len(it.keys)))()
+            for j, key in enumerate(it.keys):
+                keys[j] = _ref_bytes(k, key)
+            value = None
+            if it.value is not None:
+                value = (CBytes * 1)(_ref_bytes(k, it.value))
+            k.refs += [ops, keys, value]
+            self.arr[i] = CProofOpsIn(ops, len(it.ops), _ref_bytes(k, it.root), keys, len(it.keys),
+                                      ctypes.cast(value, ctypes.POINTER(CBytes)) if value is not None else None)
+        self.results = (ctypes.c_int32 * max(1, n))()
+        self.errs = ctypes.create_string_buffer(ERR_STRIDE * max(1, n))
+
+    def call(self, ctx, lib=None, n=None) -> int:
+        """The C call alone, over the first n items (default all): the number of failed items."""
+        L = _setup_proof_ops(lib or _native.lib())
+        rc = L.tmv_proof_ops_verify(_handle(ctx), self.arr, self.n if n is None else n, self.results, self.errs, ERR_STRIDE)
+        if rc < 0:
+            raise NativeError(f"tmv_proof_ops_verify failed ({rc})")
+        return rc
+
+    def run(self, ctx, lib=None) -> List[Optional[str]]:
+        self.call(ctx, lib)
+        return _texts(self.results, self.errs, self.n)
+
+
+def proof_ops_verify(ctx, items: List[ProofOpsItem], lib=None) -> List[Optional[str]]:
+    """ProofRuntime.Verify(proof, root, keypath, args) of each item under merkle.DefaultProofRuntime():
+    None or the reference's error text (cut to ERR_STRIDE - 1 bytes)."""
+    return PreparedProofOps(items).run(ctx, lib)
+
+
+class PreparedTxProofs:
+    """The C array of a tmv_tx_proofs_validate call, built once."""
+
+    def __init__(self, items: List[TxProof]):
+        self.k = k = _Keep()
+        self.n = n = len(items)
+        self.arr = (CTxProofIn * max(1, n))()
+        for i, it in enumerate(items):
+            self.arr[i] = CTxProofIn(_ref_bytes(k, it.root_hash), _ref_bytes(k, it.data), _c_proof(k, it.proof),
+                                     _ref_bytes(k, it.data_hash))
+        self.results = (ctypes.c_int32 * max(1, n))()
+        self.errs = ctypes.create_string_buffer(ERR_STRIDE * max(1, n))
+
+    def call(self, ctx, lib=None, n=None) -> int:
+        """The C call alone, over the first n items (default all): the number of failed items."""
+        L = _setup_proof_ops(lib or _native.lib())
+        rc = L.tmv_tx_proofs_validate(_handle(ctx), self.arr, self.n if n is None else n, self.results, self.errs, ERR_STRIDE)
+        if rc < 0:
+            raise NativeError(f"tmv_tx_proofs_validate failed ({rc})")
+        return rc
+
+    def run(self, ctx, lib=None) -> List[Optional[str]]:
+        self.call(ctx, lib)
+        return _texts(self.results, self.errs, self.n)
+
+
+def tx_proofs_validate(ctx, items: List[TxProof], lib=None) -> List[Optional[str]]:
+    """TxProof.Validate(dataHash) of each item: None or the reference's error text."""
+    return PreparedTxProofs(items).run(ctx, lib)
+
+
 # ---------------------------------------------------------------- blocks
 # tmv_commit_hash_many / tmv_blocks_validate_basic (include/tmhost.h): Commit.Hash
 # (types/block.go:900-918) and Block.ValidateBasic (types/block.go:53-94).
