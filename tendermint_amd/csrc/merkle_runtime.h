@@ -1,10 +1,10 @@
-// tmv_merkle_proofs / tmv_merkle_verify_proofs / tmv_merkle_aunt_offsets
-// (include/tmverify.h): merkle.ProofsFromByteSlices (crypto/merkle/proof.go:
-// 33-48) and Proof.Verify (proof.go:52-68) behind the C-ABI.  Kept out of
-// tmverify_runtime.cpp, which includes this file at its end: the entry points
-// share its Device, staging buffers, bounded waits and error text.
-// Synchronous, host buffers, device 0; staged like tmv_merkle_roots: one H2D
-// copy, the launches (merkle_proof_kernels.hip), one D2H copy.
+// tmv_merkle_roots / tmv_merkle_proofs / tmv_merkle_verify_proofs /
+// tmv_merkle_aunt_offsets (include/tmverify.h): merkle.HashFromByteSlices
+// (crypto/merkle/tree.go:11-21), ProofsFromByteSlices (proof.go:33-48) and
+// Proof.Verify (proof.go:52-68) behind the C-ABI.  Kept out of
+// tmverify_runtime.cpp, which includes this file at its end.  Staged calls
+// (staged_call.h) with the launches of merkle_kernels.hip and
+// merkle_proof_kernels.hip.
 #pragma once
 #include "host/merkle_plan.h"
 #include "merkle_proof.h"
@@ -22,7 +22,7 @@ uint32_t merkle_long_min() {
   return v;
 }
 
-// The checks tmv_merkle_roots makes on its offsets; bytes and max_leaves out.
+// The checks on the leaves of n_trees trees; max_leaves out.
 int merkle_check_offsets(const char *who, const uint8_t *data, const uint32_t *leaf_off, uint32_t n_leaves,
                          const uint32_t *tree_off, uint32_t n_trees, uint32_t *max_leaves) {
   const std::string w(who);
@@ -31,13 +31,9 @@ int merkle_check_offsets(const char *who, const uint8_t *data, const uint32_t *l
     set_error(w + ": offsets must start at 0 and tree_off must end at n_leaves");
     return TMV_ERR_ARG;
   }
-  *max_leaves = 0;
-  for (uint32_t t = 0; t < n_trees; t++) {
-    if (tree_off[t + 1] < tree_off[t]) { set_error(w + ": tree_off decreasing"); return TMV_ERR_ARG; }
-    *max_leaves = std::max(*max_leaves, tree_off[t + 1] - tree_off[t]);
-  }
-  for (uint32_t i = 0; i < n_leaves; i++)
-    if (leaf_off[i + 1] < leaf_off[i]) { set_error(w + ": leaf_off decreasing"); return TMV_ERR_ARG; }
+  int rc = offsets_rc(who, "tree_off", tree_off, n_trees, max_leaves);
+  if (rc == 0) rc = offsets_rc(who, "leaf_off", leaf_off, n_leaves);
+  if (rc) return rc;
   const uint32_t bytes = leaf_off[n_leaves];
   if (bytes && !data) { set_error(w + ": null data"); return TMV_ERR_ARG; }
   if (n_leaves > (1u << 26) || bytes > (1u << 30)) { set_error(w + ": input too large"); return TMV_ERR_ARG; }
@@ -79,9 +75,8 @@ extern "C" {
 
 int tmv_merkle_aunt_offsets(const uint32_t *tree_off, uint32_t n_trees, uint32_t *aunt_off_out) {
   if (!tree_off || !aunt_off_out) { set_error("tmv_merkle_aunt_offsets: null pointer"); return TMV_ERR_ARG; }
-  if (tree_off[0] != 0) { set_error("tmv_merkle_aunt_offsets: tree_off[0] must be 0"); return TMV_ERR_ARG; }
-  for (uint32_t t = 0; t < n_trees; t++)
-    if (tree_off[t + 1] < tree_off[t]) { set_error("tmv_merkle_aunt_offsets: tree_off decreasing"); return TMV_ERR_ARG; }
+  const int rc = offsets_rc("tmv_merkle_aunt_offsets", "tree_off", tree_off, n_trees);
+  if (rc) return rc;
   if (tree_off[n_trees] > (1u << 26)) { set_error("tmv_merkle_aunt_offsets: input too large"); return TMV_ERR_ARG; }
   if (tmh::merkle_aunt_offsets(tree_off, n_trees, aunt_off_out) != 0) {
     set_error("tmv_merkle_aunt_offsets: aunt count exceeds 32 bits");
@@ -90,18 +85,48 @@ int tmv_merkle_aunt_offsets(const uint32_t *tree_off, uint32_t n_trees, uint32_t
   return 0;
 }
 
+int tmv_merkle_roots(tmv_ctx *ctx, const uint8_t *data, const uint32_t *leaf_off, uint32_t n_leaves,
+                     const uint32_t *tree_off, uint32_t n_trees, uint8_t *hash_out) {
+  StagedCall c;
+  int rc = c.attach(ctx);
+  if (rc) return rc;
+  if (n_trees == 0) return 0;
+  if (!hash_out) { set_error("tmv_merkle_roots: null pointer"); return TMV_ERR_ARG; }
+  uint32_t max_leaves = 0;
+  if ((rc = merkle_check_offsets("tmv_merkle_roots", data, leaf_off, n_leaves, tree_off, n_trees, &max_leaves)) != 0)
+    return rc;
+  const uint32_t bytes = leaf_off[n_leaves];
+  if ((rc = c.open()) != 0) return rc;
+  tmh::StageLayout L;
+  const size_t o_leaf = L.in(4ull * (n_leaves + 1)), o_tree = L.in(4ull * (n_trees + 1)), o_data = L.in(bytes);
+  const size_t o_na = L.scratch(32ull * n_leaves), o_nb = L.scratch(32ull * n_leaves);  // two node arrays
+  const size_t o_out = L.out(32ull * n_trees);
+  if ((rc = c.reserve(L, c.d->h_stage, c.d->d_stage, false)) != 0) return rc;
+  c.put(o_leaf, leaf_off, 4ull * (n_leaves + 1));
+  c.put(o_tree, tree_off, 4ull * (n_trees + 1));
+  c.put(o_data, data, bytes);
+  if ((rc = c.upload("hipMemcpyAsync(merkle)")) != 0) return rc;
+  const hipError_t e = tmv::launch_merkle_roots(c.g + o_data, c.dev<const uint32_t>(o_leaf), n_leaves,
+                                                c.dev<const uint32_t>(o_tree), n_trees, max_leaves,
+                                                c.dev<uint32_t>(o_na), c.dev<uint32_t>(o_nb), c.g + o_out, c.s);
+  if (e != hipSuccess) { set_error("merkle launch", e); return TMV_ERR_LAUNCH; }
+  return c.finish("merkle readback", hash_out, 32ull * n_trees);
+}
+
 int tmv_merkle_proofs(tmv_ctx *ctx, uint32_t flags, const uint8_t *data, const uint32_t *leaf_off, uint32_t n_leaves,
                       const uint32_t *tree_off, uint32_t n_trees, uint8_t *root_out, uint8_t *leaf_hash_out,
                       const uint32_t *aunt_off, uint8_t *aunts_out) {
-  if (!ctx || ctx->devs.empty()) { set_error("null context"); return TMV_ERR_ARG; }
+  StagedCall c;
+  int rc = c.attach(ctx);
+  if (rc) return rc;
   if (n_trees == 0) return 0;
   if (!root_out || (n_leaves && !leaf_hash_out) || (aunts_out && !aunt_off)) {
     set_error("tmv_merkle_proofs: null pointer");
     return TMV_ERR_ARG;
   }
   uint32_t max_leaves = 0;
-  int rc = merkle_check_offsets("tmv_merkle_proofs", data, leaf_off, n_leaves, tree_off, n_trees, &max_leaves);
-  if (rc) return rc;
+  if ((rc = merkle_check_offsets("tmv_merkle_proofs", data, leaf_off, n_leaves, tree_off, n_trees, &max_leaves)) != 0)
+    return rc;
   const uint32_t bytes = leaf_off[n_leaves];
   const int kernel = merkle_leaf_kernel("tmv_merkle_proofs", flags, n_leaves, bytes);
   if (kernel < 0) return kernel;
@@ -115,54 +140,30 @@ int tmv_merkle_proofs(tmv_ctx *ctx, uint32_t flags, const uint8_t *data, const u
     }
     n_aunts = aunt_off[n_leaves];
   }
-  Device &d = *ctx->devs[0];
-  std::lock_guard<std::mutex> lk(d.mu);
-  if (d.faulted) return faulted_rc(d);
-  hipError_t e = hipSetDevice(d.id);
-  if (e != hipSuccess) { set_error("hipSetDevice", e); return TMV_ERR_NO_DEVICE; }
-  // staging: leaf_off | tree_off | aunt_off | 16 bytes of padding | data, then (device only) the leaf
-  // nodes, the arena of upper levels, and the outputs roots | leaf hashes | aunts
-  const size_t o_tree = align16(4ull * (n_leaves + 1)), o_aunt = o_tree + align16(4ull * (n_trees + 1));
-  const size_t o_data = o_aunt + (aunts_out ? align16(4ull * (n_leaves + 1)) : 0) + 16;
-  const size_t in_bytes = o_data + align16(bytes);
-  const size_t o_leafn = in_bytes, o_arena = o_leafn + 32ull * n_leaves;
-  const size_t o_out = o_arena + 32ull * tmh::merkle_arena_nodes(n_leaves, n_trees);
-  const size_t q_leaf = 32ull * n_trees, q_aunts = q_leaf + 32ull * n_leaves, out_bytes = q_aunts + 32ull * n_aunts;
-  hipStream_t s = context_stream(d);
-  if (!s) { set_error("hipStreamCreate failed"); return TMV_ERR_NO_DEVICE; }
-  if ((e = wait_stream(d, s)) != hipSuccess) return wait_rc(e);  // staging shared with tmv_merkle_roots
-  if ((e = d.h_valset.ensure(std::max(in_bytes, out_bytes), true)) != hipSuccess) {
-    set_error("hipHostMalloc", e);
-    return TMV_ERR_NOMEM;
-  }
-  if ((e = d.d_valset.ensure(o_out + out_bytes, false)) != hipSuccess) { set_error("hipMalloc", e); return TMV_ERR_NOMEM; }
-  uint8_t *h = static_cast<uint8_t *>(d.h_valset.ptr);
-  std::memcpy(h, leaf_off, 4ull * (n_leaves + 1));
-  std::memcpy(h + o_tree, tree_off, 4ull * (n_trees + 1));
-  if (aunts_out) std::memcpy(h + o_aunt, aunt_off, 4ull * (n_leaves + 1));
-  std::memset(h + o_data - 16, 0, 16);
-  if (bytes) std::memcpy(h + o_data, data, bytes);
-  uint8_t *g = static_cast<uint8_t *>(d.d_valset.ptr);
-  if ((e = hipMemcpyAsync(g, h, in_bytes, hipMemcpyHostToDevice, s)) != hipSuccess) {
-    set_error("hipMemcpyAsync(merkle proofs)", e);
-    return TMV_ERR_LAUNCH;
-  }
-  uint32_t *leafn = reinterpret_cast<uint32_t *>(g + o_leafn);
-  e = merkle_launch_leaves(kernel, flags, g + o_data, reinterpret_cast<const uint32_t *>(g), n_leaves, leafn, s);
+  if ((rc = c.open()) != 0) return rc;
+  tmh::StageLayout L;
+  const size_t o_leaf = L.in(4ull * (n_leaves + 1)), o_tree = L.in(4ull * (n_trees + 1));
+  const size_t o_aunt = L.in(aunts_out ? 4ull * (n_leaves + 1) : 0), o_data = L.in_padded(bytes);
+  const size_t o_leafn = L.scratch(32ull * n_leaves);  // the leaf nodes, then the arena of upper levels
+  const size_t o_arena = L.scratch(32ull * tmh::merkle_arena_nodes(n_leaves, n_trees));
+  const size_t o_root = L.out(32ull * n_trees), o_lh = L.out(32ull * n_leaves), o_aunts = L.out(32ull * n_aunts);
+  if ((rc = c.reserve(L, c.d->h_stage, c.d->d_stage, true)) != 0) return rc;
+  c.put(o_leaf, leaf_off, 4ull * (n_leaves + 1));
+  c.put(o_tree, tree_off, 4ull * (n_trees + 1));
+  if (aunts_out) c.put(o_aunt, aunt_off, 4ull * (n_leaves + 1));
+  c.put(o_data, data, bytes);
+  if ((rc = c.upload("hipMemcpyAsync(merkle proofs)")) != 0) return rc;
+  uint32_t *leafn = c.dev<uint32_t>(o_leafn);
+  hipError_t e = merkle_launch_leaves(kernel, flags, c.g + o_data, c.dev<const uint32_t>(o_leaf), n_leaves, leafn, c.s);
   if (e == hipSuccess)
-    e = tmv::launch_merkle_proofs(reinterpret_cast<const uint32_t *>(g + o_tree), n_trees, n_leaves, max_leaves, leafn,
-                                  reinterpret_cast<uint32_t *>(g + o_arena),
-                                  reinterpret_cast<const uint32_t *>(g + o_aunt), g + o_out, g + o_out + q_leaf,
-                                  aunts_out ? g + o_out + q_aunts : nullptr, s);
+    e = tmv::launch_merkle_proofs(c.dev<const uint32_t>(o_tree), n_trees, n_leaves, max_leaves, leafn,
+                                  c.dev<uint32_t>(o_arena), c.dev<const uint32_t>(o_aunt), c.g + o_root, c.g + o_lh,
+                                  aunts_out ? c.g + o_aunts : nullptr, c.s);
   if (e != hipSuccess) { set_error("merkle proofs launch", e); return TMV_ERR_LAUNCH; }
-  if ((e = hipMemcpyAsync(h, g + o_out, out_bytes, hipMemcpyDeviceToHost, s)) != hipSuccess ||
-      (e = wait_stream(d, s)) != hipSuccess) {
-    if (e != hipErrorNotReady) set_error("merkle proofs readback", e);
-    return wait_rc(e);
-  }
-  std::memcpy(root_out, h, 32ull * n_trees);
-  if (n_leaves) std::memcpy(leaf_hash_out, h + q_leaf, 32ull * n_leaves);
-  if (n_aunts) std::memcpy(aunts_out, h + q_aunts, 32ull * n_aunts);
+  if ((rc = c.finish("merkle proofs readback")) != 0) return rc;
+  std::memcpy(root_out, c.result(o_root), 32ull * n_trees);
+  if (n_leaves) std::memcpy(leaf_hash_out, c.result(o_lh), 32ull * n_leaves);
+  if (n_aunts) std::memcpy(aunts_out, c.result(o_aunts), 32ull * n_aunts);
   return 0;
 }
 
@@ -170,16 +171,16 @@ int tmv_merkle_verify_proofs(tmv_ctx *ctx, uint32_t flags, uint32_t n, const int
                              const uint8_t *leaf_hash, const uint8_t *aunts, const uint32_t *aunt_off,
                              const uint8_t *root, const uint8_t *data, const uint32_t *leaf_off, int8_t *status_out,
                              uint8_t *leaf_hash_calc, uint8_t *root_calc, uint8_t *root_nil) {
-  if (!ctx || ctx->devs.empty()) { set_error("null context"); return TMV_ERR_ARG; }
+  StagedCall c;
+  int rc = c.attach(ctx);
+  if (rc) return rc;
   if (n == 0) return 0;
   if (!total || !index || !leaf_hash || !aunt_off || !root || !status_out) {
     set_error("tmv_merkle_verify_proofs: null pointer");
     return TMV_ERR_ARG;
   }
   if (n > (1u << 26)) { set_error("tmv_merkle_verify_proofs: input too large"); return TMV_ERR_ARG; }
-  if (aunt_off[0] != 0) { set_error("tmv_merkle_verify_proofs: aunt_off[0] must be 0"); return TMV_ERR_ARG; }
-  for (uint32_t i = 0; i < n; i++)
-    if (aunt_off[i + 1] < aunt_off[i]) { set_error("tmv_merkle_verify_proofs: aunt_off decreasing"); return TMV_ERR_ARG; }
+  if ((rc = offsets_rc("tmv_merkle_verify_proofs", "aunt_off", aunt_off, n)) != 0) return rc;
   const uint32_t n_aunts = aunt_off[n];
   if (n_aunts > (1u << 28)) { set_error("tmv_merkle_verify_proofs: input too large"); return TMV_ERR_ARG; }
   if (n_aunts && !aunts) { set_error("tmv_merkle_verify_proofs: null aunts"); return TMV_ERR_ARG; }
@@ -188,70 +189,43 @@ int tmv_merkle_verify_proofs(tmv_ctx *ctx, uint32_t flags, uint32_t n, const int
   int kernel = 0;
   if (!given) {
     if (!leaf_off) { set_error("tmv_merkle_verify_proofs: null pointer"); return TMV_ERR_ARG; }
-    if (leaf_off[0] != 0) { set_error("tmv_merkle_verify_proofs: leaf_off[0] must be 0"); return TMV_ERR_ARG; }
-    for (uint32_t i = 0; i < n; i++)
-      if (leaf_off[i + 1] < leaf_off[i]) { set_error("tmv_merkle_verify_proofs: leaf_off decreasing"); return TMV_ERR_ARG; }
+    if ((rc = offsets_rc("tmv_merkle_verify_proofs", "leaf_off", leaf_off, n)) != 0) return rc;
     bytes = leaf_off[n];
     if (bytes && !data) { set_error("tmv_merkle_verify_proofs: null data"); return TMV_ERR_ARG; }
     if (bytes > (1u << 30)) { set_error("tmv_merkle_verify_proofs: input too large"); return TMV_ERR_ARG; }
     kernel = merkle_leaf_kernel("tmv_merkle_verify_proofs", flags, n, bytes);
     if (kernel < 0) return kernel;
   }
-  Device &d = *ctx->devs[0];
-  std::lock_guard<std::mutex> lk(d.mu);
-  if (d.faulted) return faulted_rc(d);
-  hipError_t e = hipSetDevice(d.id);
-  if (e != hipSuccess) { set_error("hipSetDevice", e); return TMV_ERR_NO_DEVICE; }
-  // staging: total | index | leaf hashes | roots | aunts | aunt_off | leaf_off | 16 bytes of padding | data,
-  // then (device only) the leaf nodes and the outputs leaf hashes | roots | statuses | nil flags
-  const size_t o_index = 8ull * n, o_lh = 2 * o_index, o_root = o_lh + 32ull * n, o_aunts = o_root + 32ull * n;
-  const size_t o_aoff = o_aunts + 32ull * n_aunts, o_loff = o_aoff + align16(4ull * (n + 1));
-  const size_t o_data = o_loff + (given ? 0 : align16(4ull * (n + 1))) + 16;
-  const size_t in_bytes = o_data + align16(bytes);
-  const size_t o_leafn = in_bytes, o_out = o_leafn + (given ? 0 : 32ull * n);
-  const size_t q_root = 32ull * n, q_status = 2 * q_root, q_nil = q_status + align16(n), out_bytes = q_nil + align16(n);
-  hipStream_t s = context_stream(d);
-  if (!s) { set_error("hipStreamCreate failed"); return TMV_ERR_NO_DEVICE; }
-  if ((e = wait_stream(d, s)) != hipSuccess) return wait_rc(e);  // staging shared with tmv_merkle_roots
-  if ((e = d.h_valset.ensure(std::max(in_bytes, out_bytes), true)) != hipSuccess) {
-    set_error("hipHostMalloc", e);
-    return TMV_ERR_NOMEM;
-  }
-  if ((e = d.d_valset.ensure(o_out + out_bytes, false)) != hipSuccess) { set_error("hipMalloc", e); return TMV_ERR_NOMEM; }
-  uint8_t *h = static_cast<uint8_t *>(d.h_valset.ptr);
-  std::memcpy(h, total, 8ull * n);
-  std::memcpy(h + o_index, index, 8ull * n);
-  std::memcpy(h + o_lh, leaf_hash, 32ull * n);
-  std::memcpy(h + o_root, root, 32ull * n);
-  if (n_aunts) std::memcpy(h + o_aunts, aunts, 32ull * n_aunts);
-  std::memcpy(h + o_aoff, aunt_off, 4ull * (n + 1));
-  if (!given) std::memcpy(h + o_loff, leaf_off, 4ull * (n + 1));
-  std::memset(h + o_data - 16, 0, 16);
-  if (bytes) std::memcpy(h + o_data, data, bytes);
-  uint8_t *g = static_cast<uint8_t *>(d.d_valset.ptr);
-  if ((e = hipMemcpyAsync(g, h, in_bytes, hipMemcpyHostToDevice, s)) != hipSuccess) {
-    set_error("hipMemcpyAsync(merkle verify)", e);
-    return TMV_ERR_LAUNCH;
-  }
-  uint32_t *leafn = given ? nullptr : reinterpret_cast<uint32_t *>(g + o_leafn);
-  if (!given)
-    e = merkle_launch_leaves(kernel, flags, g + o_data, reinterpret_cast<const uint32_t *>(g + o_loff), n, leafn, s);
+  if ((rc = c.open()) != 0) return rc;
+  tmh::StageLayout L;
+  const size_t o_total = L.in(8ull * n), o_index = L.in(8ull * n), o_lh = L.in(32ull * n), o_root = L.in(32ull * n);
+  const size_t o_aunts = L.in(32ull * n_aunts), o_aoff = L.in(4ull * (n + 1));
+  const size_t o_loff = L.in(given ? 0 : 4ull * (n + 1)), o_data = L.in_padded(bytes);
+  const size_t o_leafn = L.scratch(given ? 0 : 32ull * n);  // the leaf nodes
+  const size_t q_lh = L.out(32ull * n), q_root = L.out(32ull * n), q_status = L.out(n), q_nil = L.out(n);
+  if ((rc = c.reserve(L, c.d->h_stage, c.d->d_stage, true)) != 0) return rc;
+  c.put(o_total, total, 8ull * n);
+  c.put(o_index, index, 8ull * n);
+  c.put(o_lh, leaf_hash, 32ull * n);
+  c.put(o_root, root, 32ull * n);
+  c.put(o_aunts, aunts, 32ull * n_aunts);
+  c.put(o_aoff, aunt_off, 4ull * (n + 1));
+  if (!given) c.put(o_loff, leaf_off, 4ull * (n + 1));
+  c.put(o_data, data, bytes);
+  if ((rc = c.upload("hipMemcpyAsync(merkle verify)")) != 0) return rc;
+  uint32_t *leafn = given ? nullptr : c.dev<uint32_t>(o_leafn);
+  hipError_t e = hipSuccess;
+  if (!given) e = merkle_launch_leaves(kernel, flags, c.g + o_data, c.dev<const uint32_t>(o_loff), n, leafn, c.s);
   if (e == hipSuccess)
-    e = tmv::launch_merkle_verify_proofs(n, reinterpret_cast<const int64_t *>(g),
-                                         reinterpret_cast<const int64_t *>(g + o_index), g + o_lh, g + o_aunts,
-                                         reinterpret_cast<const uint32_t *>(g + o_aoff), g + o_root, leafn,
-                                         reinterpret_cast<int8_t *>(g + o_out + q_status), g + o_out,
-                                         g + o_out + q_root, g + o_out + q_nil, s);
+    e = tmv::launch_merkle_verify_proofs(n, c.dev<const int64_t>(o_total), c.dev<const int64_t>(o_index), c.g + o_lh,
+                                         c.g + o_aunts, c.dev<const uint32_t>(o_aoff), c.g + o_root, leafn,
+                                         c.dev<int8_t>(q_status), c.g + q_lh, c.g + q_root, c.g + q_nil, c.s);
   if (e != hipSuccess) { set_error("merkle verify launch", e); return TMV_ERR_LAUNCH; }
-  if ((e = hipMemcpyAsync(h, g + o_out, out_bytes, hipMemcpyDeviceToHost, s)) != hipSuccess ||
-      (e = wait_stream(d, s)) != hipSuccess) {
-    if (e != hipErrorNotReady) set_error("merkle verify readback", e);
-    return wait_rc(e);
-  }
-  std::memcpy(status_out, h + q_status, n);
-  if (leaf_hash_calc) std::memcpy(leaf_hash_calc, h, 32ull * n);
-  if (root_calc) std::memcpy(root_calc, h + q_root, 32ull * n);
-  if (root_nil) std::memcpy(root_nil, h + q_nil, n);
+  if ((rc = c.finish("merkle verify readback")) != 0) return rc;
+  std::memcpy(status_out, c.result(q_status), n);
+  if (leaf_hash_calc) std::memcpy(leaf_hash_calc, c.result(q_lh), 32ull * n);
+  if (root_calc) std::memcpy(root_calc, c.result(q_root), 32ull * n);
+  if (root_nil) std::memcpy(root_nil, c.result(q_nil), n);
   bool all = true;
   for (uint32_t i = 0; i < n; i++) all = all && status_out[i] == 0;
   return all ? 0 : 1;

@@ -35,6 +35,7 @@
 #include "host/shard_plan.h"
 #include "host/stream_plan.h"
 #include "host/shard_run.h"
+#include "host/stage_layout.h"
 #include "host/wait.h"
 #include "knobs.h"
 #include "ktimer.h"
@@ -55,7 +56,7 @@ void set_error(const char *where, hipError_t e) {
 }
 void set_error(const std::string &s) { g_last_error = s; }
 
-inline size_t align16(size_t x) { return (x + 15) & ~size_t(15); }
+using tmh::align16;
 
 // Large staging copies into pinned memory use several host threads (one
 // thread moves ~10 GB/s; a 1M-signature batch is ~220 MB).
@@ -259,7 +260,7 @@ struct Device {
   // first such launch
   unsigned long long *ent_total = nullptr;
   bool ent_tried = false;
-  DeviceBuf d_valset, h_valset;  // tmv_validator_set_hashes staging
+  DeviceBuf d_stage, h_stage;  // the staged calls' buffers (staged_call.h), secp256k1 apart
   uint32_t *d_secp_gtab = nullptr;             // secp256k1: j G, j = 1..15, affine (secp256k1.h)
   DeviceBuf d_secp_in, h_secp_in, d_secp_work; // tmv_secp256k1_verify_batch staging and workspace
   // secp256k1 key cache (secp256k1.h, comb tables): device slots of 61,440
@@ -699,6 +700,9 @@ struct tmv_ctx {
     }
   }
 };
+
+// StagedCall: the synchronous host-buffer entry points' plumbing
+#include "staged_call.h"
 
 // Options of one launch of n entries: per-entry or batch equation (flags,
 // else TMV_MSM_MIN), parameters and fresh randomness.
@@ -2703,120 +2707,6 @@ int tmv_verify_batches_device(tmv_ctx *ctx, int device, uint8_t key_kind, uint32
   return TMV_NOT_ALL;
 }
 
-// ValidatorSet.Hash of many sets in one launch (SURVEY §8(f) rank 4;
-// types/validator_set.go:344-350).  Synchronous, host buffers.
-int tmv_validator_set_hashes(tmv_ctx *ctx, const uint8_t *pk, const uint8_t *key_kind, const int64_t *power,
-                             const uint32_t *set_off, uint32_t n_sets, uint8_t *hash_out) {
-  if (!ctx || ctx->devs.empty()) { set_error("null context"); return TMV_ERR_ARG; }
-  if (n_sets == 0) return 0;
-  if (!set_off || !hash_out) { set_error("tmv_validator_set_hashes: null pointer"); return TMV_ERR_ARG; }
-  if (set_off[0] != 0) { set_error("tmv_validator_set_hashes: set_off[0] must be 0"); return TMV_ERR_ARG; }
-  for (uint32_t s = 0; s < n_sets; s++)
-    if (set_off[s + 1] < set_off[s]) { set_error("tmv_validator_set_hashes: set_off decreasing"); return TMV_ERR_ARG; }
-  const uint32_t n = set_off[n_sets];
-  if (n && (!pk || !key_kind || !power)) { set_error("tmv_validator_set_hashes: null pointer"); return TMV_ERR_ARG; }
-  if (n > (1u << 26)) { set_error("tmv_validator_set_hashes: too many validators"); return TMV_ERR_ARG; }
-  for (uint32_t i = 0; i < n; i++)
-    if (key_kind[i] != TMV_KIND_ED25519 && key_kind[i] != TMV_KIND_SR25519) {
-      set_error("tmv_validator_set_hashes: key kind must be ed25519 or sr25519");
-      return TMV_ERR_ARG;
-    }
-  Device &d = *ctx->devs[0];
-  std::lock_guard<std::mutex> lk(d.mu);
-  if (d.faulted) return faulted_rc(d);
-  hipError_t e = hipSetDevice(d.id);
-  if (e != hipSuccess) { set_error("hipSetDevice", e); return TMV_ERR_NO_DEVICE; }
-  // staging: power | set_off | pk | kind, then (device only) two node arrays and the roots
-  const size_t o_off = align16(8ull * n), o_pk = o_off + align16(4ull * (n_sets + 1));
-  const size_t o_kind = o_pk + align16(32ull * n), in_bytes = o_kind + align16(n);
-  const size_t o_na = in_bytes, o_nb = o_na + 32ull * n, o_out = o_nb + 32ull * n;
-  const size_t dev_bytes = o_out + 32ull * n_sets;
-  hipStream_t s = context_stream(d);
-  if (!s) { set_error("hipStreamCreate failed"); return TMV_ERR_NO_DEVICE; }
-  if ((e = wait_stream(d, s)) != hipSuccess) return wait_rc(e);  // staging may still feed an earlier call
-  if ((e = d.h_valset.ensure(in_bytes, true)) != hipSuccess) { set_error("hipHostMalloc", e); return TMV_ERR_NOMEM; }
-  if ((e = d.d_valset.ensure(dev_bytes, false)) != hipSuccess) { set_error("hipMalloc", e); return TMV_ERR_NOMEM; }
-  uint8_t *h = static_cast<uint8_t *>(d.h_valset.ptr);
-  if (n) {
-    std::memcpy(h, power, 8ull * n);
-    std::memcpy(h + o_pk, pk, 32ull * n);
-    std::memcpy(h + o_kind, key_kind, n);
-  }
-  std::memcpy(h + o_off, set_off, 4ull * (n_sets + 1));
-  uint8_t *g = static_cast<uint8_t *>(d.d_valset.ptr);
-  if ((e = hipMemcpyAsync(g, h, in_bytes, hipMemcpyHostToDevice, s)) != hipSuccess) {
-    set_error("hipMemcpyAsync(valset)", e);
-    return TMV_ERR_LAUNCH;
-  }
-  e = tmv::launch_valset_hashes(g + o_pk, g + o_kind, reinterpret_cast<const int64_t *>(g), n,
-                                reinterpret_cast<const uint32_t *>(g + o_off), n_sets,
-                                reinterpret_cast<uint32_t *>(g + o_na), reinterpret_cast<uint32_t *>(g + o_nb),
-                                g + o_out, s);
-  if (e != hipSuccess) { set_error("valset hash launch", e); return TMV_ERR_LAUNCH; }
-  if ((e = hipMemcpyAsync(hash_out, g + o_out, 32ull * n_sets, hipMemcpyDeviceToHost, s)) != hipSuccess ||
-      (e = wait_stream(d, s)) != hipSuccess) {
-    if (e != hipErrorNotReady) set_error("valset hash readback", e);
-    return wait_rc(e);
-  }
-  return 0;
-}
-
-int tmv_merkle_roots(tmv_ctx *ctx, const uint8_t *data, const uint32_t *leaf_off, uint32_t n_leaves,
-                     const uint32_t *tree_off, uint32_t n_trees, uint8_t *hash_out) {
-  if (!ctx || ctx->devs.empty()) { set_error("null context"); return TMV_ERR_ARG; }
-  if (n_trees == 0) return 0;
-  if (!leaf_off || !tree_off || !hash_out) { set_error("tmv_merkle_roots: null pointer"); return TMV_ERR_ARG; }
-  if (leaf_off[0] != 0 || tree_off[0] != 0 || tree_off[n_trees] != n_leaves) {
-    set_error("tmv_merkle_roots: offsets must start at 0 and tree_off must end at n_leaves");
-    return TMV_ERR_ARG;
-  }
-  uint32_t max_leaves = 0;
-  for (uint32_t t = 0; t < n_trees; t++) {
-    if (tree_off[t + 1] < tree_off[t]) { set_error("tmv_merkle_roots: tree_off decreasing"); return TMV_ERR_ARG; }
-    max_leaves = std::max(max_leaves, tree_off[t + 1] - tree_off[t]);
-  }
-  for (uint32_t i = 0; i < n_leaves; i++)
-    if (leaf_off[i + 1] < leaf_off[i]) { set_error("tmv_merkle_roots: leaf_off decreasing"); return TMV_ERR_ARG; }
-  const uint32_t bytes = leaf_off[n_leaves];
-  if (bytes && !data) { set_error("tmv_merkle_roots: null data"); return TMV_ERR_ARG; }
-  if (n_leaves > (1u << 26) || bytes > (1u << 30)) { set_error("tmv_merkle_roots: input too large"); return TMV_ERR_ARG; }
-  Device &d = *ctx->devs[0];
-  std::lock_guard<std::mutex> lk(d.mu);
-  if (d.faulted) return faulted_rc(d);
-  hipError_t e = hipSetDevice(d.id);
-  if (e != hipSuccess) { set_error("hipSetDevice", e); return TMV_ERR_NO_DEVICE; }
-  // staging: leaf_off | tree_off | data, then (device only) two node arrays and the roots
-  const size_t o_tree = align16(4ull * (n_leaves + 1)), o_data = o_tree + align16(4ull * (n_trees + 1));
-  const size_t in_bytes = o_data + align16(bytes);
-  const size_t o_na = in_bytes, o_nb = o_na + 32ull * n_leaves, o_out = o_nb + 32ull * n_leaves;
-  const size_t dev_bytes = o_out + 32ull * n_trees;
-  hipStream_t s = context_stream(d);
-  if (!s) { set_error("hipStreamCreate failed"); return TMV_ERR_NO_DEVICE; }
-  if ((e = wait_stream(d, s)) != hipSuccess) return wait_rc(e);  // staging shared with tmv_validator_set_hashes
-  if ((e = d.h_valset.ensure(in_bytes, true)) != hipSuccess) { set_error("hipHostMalloc", e); return TMV_ERR_NOMEM; }
-  if ((e = d.d_valset.ensure(dev_bytes, false)) != hipSuccess) { set_error("hipMalloc", e); return TMV_ERR_NOMEM; }
-  uint8_t *h = static_cast<uint8_t *>(d.h_valset.ptr);
-  std::memcpy(h, leaf_off, 4ull * (n_leaves + 1));
-  std::memcpy(h + o_tree, tree_off, 4ull * (n_trees + 1));
-  if (bytes) std::memcpy(h + o_data, data, bytes);
-  uint8_t *g = static_cast<uint8_t *>(d.d_valset.ptr);
-  if ((e = hipMemcpyAsync(g, h, in_bytes, hipMemcpyHostToDevice, s)) != hipSuccess) {
-    set_error("hipMemcpyAsync(merkle)", e);
-    return TMV_ERR_LAUNCH;
-  }
-  e = tmv::launch_merkle_roots(g + o_data, reinterpret_cast<const uint32_t *>(g), n_leaves,
-                               reinterpret_cast<const uint32_t *>(g + o_tree), n_trees, max_leaves,
-                               reinterpret_cast<uint32_t *>(g + o_na), reinterpret_cast<uint32_t *>(g + o_nb),
-                               g + o_out, s);
-  if (e != hipSuccess) { set_error("merkle launch", e); return TMV_ERR_LAUNCH; }
-  if ((e = hipMemcpyAsync(hash_out, g + o_out, 32ull * n_trees, hipMemcpyDeviceToHost, s)) != hipSuccess ||
-      (e = wait_stream(d, s)) != hipSuccess) {
-    if (e != hipErrorNotReady) set_error("merkle readback", e);
-    return wait_rc(e);
-  }
-  return 0;
-}
-
 }  // extern "C"
 
 // secp256k1 key cache: the slot of every entry of one call, allocating slots
@@ -2937,93 +2827,81 @@ static void secp_keys_settle(Device &d) {
 }
 
 // secp256k1 ECDSA batch (crypto/secp256k1/secp256k1.go:206-226 per entry).
-// Synchronous, host buffers, device 0; staged like tmv_merkle_roots: one H2D
-// copy (keys padded to 48 bytes), the launches (in chunks that bound the
-// workspace), one D2H copy.  cache: verify against the keys' combs on the
-// device (secp_keys_resolve), building the missing ones on the same stream
-// ahead of the verification; the staging then carries slots in place of keys.
+// A staged call (staged_call.h) with buffers of its own: keys padded to 48
+// bytes, the launches in chunks that bound the workspace.  cache: verify
+// against the keys' combs on the device (secp_keys_resolve), building the
+// missing ones on the same stream ahead of the verification; the staging then
+// carries slots in place of keys.
 static int secp256k1_batch(tmv_ctx *ctx, bool cache, const uint8_t *pk, const uint8_t *sig, const uint8_t *msg,
                            const uint32_t *msg_off, uint32_t n, uint8_t *valid_out) {
-  if (!ctx || ctx->devs.empty()) { set_error("null context"); return TMV_ERR_ARG; }
+  StagedCall c;
+  int rc = c.attach(ctx);
+  if (rc) return rc;
   if (n == 0) return TMV_NOT_ALL;
   if (!pk || !sig || !msg_off || !valid_out) { set_error("tmv_secp256k1_verify_batch: null pointer"); return TMV_ERR_ARG; }
   if (n > (1u << 26)) { set_error("tmv_secp256k1_verify_batch: too many entries"); return TMV_ERR_ARG; }
-  if (msg_off[0] != 0) { set_error("tmv_secp256k1_verify_batch: msg_off[0] must be 0"); return TMV_ERR_ARG; }
-  for (uint32_t i = 0; i < n; i++)
-    if (msg_off[i + 1] < msg_off[i]) { set_error("tmv_secp256k1_verify_batch: msg_off decreasing"); return TMV_ERR_ARG; }
+  if ((rc = offsets_rc("tmv_secp256k1_verify_batch", "msg_off", msg_off, n)) != 0) return rc;
   const uint32_t bytes = msg_off[n];
   if (bytes > (1u << 30)) { set_error("tmv_secp256k1_verify_batch: messages too large"); return TMV_ERR_ARG; }
   if (bytes && !msg) { set_error("tmv_secp256k1_verify_batch: null msg"); return TMV_ERR_ARG; }
   ctx->count_call(n);
-  Device &d = *ctx->devs[0];
-  std::lock_guard<std::mutex> lk(d.mu);
-  if (d.faulted) return faulted_rc(d);
-  hipError_t e = hipSetDevice(d.id);
-  if (e != hipSuccess) { set_error("hipSetDevice", e); return TMV_ERR_NO_DEVICE; }
+  // with the stream idle no launch reads a key slot that a miss of this call may evict
+  if ((rc = c.open()) != 0) return rc;
+  Device &d = *c.d;
   constexpr uint32_t kChunk = 262144;  // entries per launch pair: 2,176 bytes of workspace each (cached: 128)
-  hipStream_t s = context_stream(d);
-  if (!s) { set_error("hipStreamCreate failed"); return TMV_ERR_NO_DEVICE; }
-  // staging may still feed an earlier call; and with the stream idle no launch
-  // reads a key slot that a miss of this call may evict
-  if ((e = wait_stream(d, s)) != hipSuccess) return wait_rc(e);
   cache = cache && secp_keys_resolve(d, pk, n) == 0;
   Device::SecpKeys &k = d.sk;
   const uint32_t nm = cache ? (uint32_t)k.miss_entry.size() : 0;
-  // staging: [pk48 |] sig | msg_off | msg [| slots | missing keys at 48 | their slots], then (device only) the
-  // statuses [and the missing keys' parse flags]
-  const size_t o_sig = cache ? 0 : 48ull * n, o_off = o_sig + 64ull * n, o_msg = o_off + align16(4ull * (n + 1));
-  const size_t o_slot = o_msg + align16(bytes), o_mpk = o_slot + (cache ? align16(4ull * n) : 0);
-  const size_t o_mslot = o_mpk + 48ull * nm, in_bytes = o_mslot + align16(4ull * nm);
-  const size_t o_out = in_bytes, o_mok = o_out + align16(n), dev_bytes = o_mok + align16(4ull * nm);
+  tmh::StageLayout L;
+  const size_t o_pk = L.in(cache ? 0 : 48ull * n), o_sig = L.in(64ull * n), o_off = L.in(4ull * (n + 1));
+  const size_t o_msg = L.in(bytes), o_slot = L.in(cache ? 4ull * n : 0);
+  const size_t o_mpk = L.in(48ull * nm), o_mslot = L.in(4ull * nm);  // the missing keys and their slots
+  const size_t o_out = L.out(n), o_mok = L.out(4ull * nm);           // statuses; the missing keys' parse flags
   // a failure from here on leaves this call's new slots unbuilt: drop the index
   struct Guard {
     Device::SecpKeys *k;
     ~Guard() { if (k) k->forget(); }
   } guard{cache ? &k : nullptr};
-  if ((e = d.h_secp_in.ensure(in_bytes, true)) != hipSuccess) { set_error("hipHostMalloc", e); return TMV_ERR_NOMEM; }
-  if ((e = d.d_secp_in.ensure(dev_bytes, false)) != hipSuccess) { set_error("hipMalloc", e); return TMV_ERR_NOMEM; }
+  if ((rc = c.reserve(L, d.h_secp_in, d.d_secp_in, false)) != 0) return rc;
   const uint32_t cn = std::min(n, kChunk);
   const size_t work_bytes = cache ? tmv::secp256k1_cached_workspace_bytes(cn) : tmv::secp256k1_workspace_bytes(cn);
+  hipError_t e;
   if ((e = d.d_secp_work.ensure(work_bytes, false)) != hipSuccess) {
     set_error("hipMalloc(secp work)", e);
     return TMV_ERR_NOMEM;
   }
-  uint8_t *h = static_cast<uint8_t *>(d.h_secp_in.ptr);
   auto pad_key = [](uint8_t *dst, const uint8_t *src) {
     std::memcpy(dst, src, 33);
     std::memset(dst + 33, 0, 15);
   };
   if (cache) {
-    std::memcpy(h + o_slot, k.slots.data(), 4ull * n);
-    for (uint32_t m = 0; m < nm; m++) pad_key(h + o_mpk + 48ull * m, pk + 33ull * k.miss_entry[m]);
-    if (nm) std::memcpy(h + o_mslot, k.miss_slot.data(), 4ull * nm);
+    c.put(o_slot, k.slots.data(), 4ull * n);
+    for (uint32_t m = 0; m < nm; m++) pad_key(c.h + o_mpk + 48ull * m, pk + 33ull * k.miss_entry[m]);
+    c.put(o_mslot, k.miss_slot.data(), 4ull * nm);
   } else {
-    for (uint32_t i = 0; i < n; i++) pad_key(h + 48ull * i, pk + 33ull * i);
+    for (uint32_t i = 0; i < n; i++) pad_key(c.h + o_pk + 48ull * i, pk + 33ull * i);
   }
-  std::memcpy(h + o_sig, sig, 64ull * n);
-  std::memcpy(h + o_off, msg_off, 4ull * (n + 1));
-  if (bytes) std::memcpy(h + o_msg, msg, bytes);
-  uint8_t *g = static_cast<uint8_t *>(d.d_secp_in.ptr);
-  if ((e = hipMemcpyAsync(g, h, in_bytes, hipMemcpyHostToDevice, s)) != hipSuccess) {
-    set_error("hipMemcpyAsync(secp256k1)", e);
-    return TMV_ERR_LAUNCH;
-  }
+  c.put(o_sig, sig, 64ull * n);
+  c.put(o_off, msg_off, 4ull * (n + 1));
+  c.put(o_msg, msg, bytes);
+  if ((rc = c.upload("hipMemcpyAsync(secp256k1)")) != 0) return rc;
+  uint8_t *g = c.g;
+  hipStream_t s = c.s;
   if (nm) {
-    e = tmv::launch_secp256k1_key_tables(g + o_mpk, reinterpret_cast<const uint32_t *>(g + o_mslot), nm, k.d_tab,
-                                         k.d_ok, reinterpret_cast<uint32_t *>(g + o_mok), s);
+    e = tmv::launch_secp256k1_key_tables(g + o_mpk, c.dev<const uint32_t>(o_mslot), nm, k.d_tab, k.d_ok,
+                                         c.dev<uint32_t>(o_mok), s);
     if (e != hipSuccess) { set_error("secp256k1 key table launch", e); return TMV_ERR_LAUNCH; }
   }
   for (uint32_t lo = 0; lo < n; lo += kChunk) {
     const uint32_t m = std::min(kChunk, n - lo);
-    const uint32_t *off = reinterpret_cast<const uint32_t *>(g + o_off) + lo;
+    const uint32_t *off = c.dev<const uint32_t>(o_off) + lo;
     uint8_t *work = static_cast<uint8_t *>(d.d_secp_work.ptr);
     if (cache)
-      e = tmv::launch_secp256k1_verify_cached(g + o_sig + 64ull * lo, g + o_msg, off,
-                                              reinterpret_cast<const uint32_t *>(g + o_slot) + lo, m, k.d_gcomb,
-                                              k.d_tab, k.d_ok, work, g + o_out + lo, s);
+      e = tmv::launch_secp256k1_verify_cached(g + o_sig + 64ull * lo, g + o_msg, off, c.dev<const uint32_t>(o_slot) + lo,
+                                              m, k.d_gcomb, k.d_tab, k.d_ok, work, g + o_out + lo, s);
     else
-      e = tmv::launch_secp256k1_verify(g + 48ull * lo, g + o_sig + 64ull * lo, g + o_msg, off, m, d.d_secp_gtab, work,
-                                       g + o_out + lo, s);
+      e = tmv::launch_secp256k1_verify(g + o_pk + 48ull * lo, g + o_sig + 64ull * lo, g + o_msg, off, m, d.d_secp_gtab,
+                                       work, g + o_out + lo, s);
     if (e != hipSuccess) { set_error("secp256k1 launch", e); return TMV_ERR_LAUNCH; }
   }
   if (nm) {
@@ -3033,11 +2911,7 @@ static int secp256k1_batch(tmv_ctx *ctx, bool cache, const uint8_t *pk, const ui
       return TMV_ERR_LAUNCH;
     }
   }
-  if ((e = hipMemcpyAsync(valid_out, g + o_out, n, hipMemcpyDeviceToHost, s)) != hipSuccess ||
-      (e = wait_stream(d, s)) != hipSuccess) {
-    if (e != hipErrorNotReady) set_error("secp256k1 readback", e);
-    return wait_rc(e);
-  }
+  if ((rc = c.finish("secp256k1 readback", valid_out, n)) != 0) return rc;
   guard.k = nullptr;
   if (nm) secp_keys_settle(d);
   bool all = true;
@@ -3124,9 +2998,11 @@ int tmv_ed25519_verify_batch_device(tmv_ctx *ctx, int device, const uint8_t *d_p
 #include "vote_ext_runtime.h"
 #undef TMV_VOTE_EXT_PART
 
-// tmv_merkle_proofs, tmv_merkle_verify_proofs, tmv_merkle_aunt_offsets
+// tmv_merkle_roots, tmv_merkle_proofs, tmv_merkle_verify_proofs, tmv_merkle_aunt_offsets,
+// tmv_merkle_value_ops
 #include "merkle_runtime.h"
 #include "merkle_ops_runtime.h"
 
-// tmv_commit_hashes
+// tmv_commit_hashes, tmv_validator_set_hashes
 #include "commit_runtime.h"
+#include "valset_runtime.h"
