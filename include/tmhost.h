@@ -472,6 +472,74 @@ typedef struct {
 int tmv_blocks_validate_basic(tmv_ctx *ctx, const tmv_block *blocks, uint32_t n, int32_t *results, char *errs,
                               size_t err_stride, uint8_t *hash_out, uint8_t *has_hash);
 
+/* ---- ABCI results and consensus params (abci/types/types.go, types/params.go) ---- */
+/* Calls with at least $TMV_DEVICE_RESULTS_MIN results (default 4096; DESIGN.md
+ * section 21) hash on the device in one tmv_tx_results_hashes call (a weak
+ * reference); smaller calls, and a build without the engine, encode and hash
+ * on the host worker pool.  Of a call that goes to the device, a tree holding
+ * a result whose data exceeds $TMV_DEVICE_RESULTS_MAX_DATA bytes (default
+ * 1024: one lane would hash it alone while the call waits, and from 4 KiB on
+ * that was measured slower) is still hashed on the host.  Both knobs are read on every call;
+ * the hashes, verdicts and texts are the same either way. */
+
+/* The deterministic fields of abci.ExecTxResult (abci/types/types.go:213-222). */
+typedef struct {
+  uint32_t code;
+  tmv_bytes data;
+  int64_t gas_wanted, gas_used;
+} tmv_tx_result;
+
+/* merkle.HashFromByteSlices over abci.MarshalTxResults(results[i]) for n lists
+ * of n_results[i] results each (results[i] may be NULL when n_results[i] is 0).
+ * first == NULL: no leading leaf, State.LastResultsHash as ApplyBlock stores it
+ * (internal/state/execution.go:262-267).  Else first[i] (may be empty) is
+ * hashed as a leaf in front of list i's results, as the light client's
+ * BlockResults does with proto.Marshal(ResponseFinalizeBlock{Events})
+ * (light/rpc/client.go:452-464).  hash_out: n x 32.  0 or < 0. */
+int tmv_results_hash_many(tmv_ctx *ctx, const tmv_tx_result *const *results, const uint32_t *n_results,
+                          const tmv_bytes *first, uint32_t n, uint8_t *hash_out);
+
+/* ConsensusParams.HashConsensusParams (types/params.go:385-399): SHA-256 of
+ * tmproto.HashedParams, [08 varint(block_max_bytes)] [10 varint(block_max_gas)]
+ * with zero fields omitted (max_gas = -1, the common case, takes 10 bytes).
+ * One hash, on the host.  0 or TMV_ERR_ARG (out == NULL). */
+int tmv_consensus_params_hash(int64_t block_max_bytes, int64_t block_max_gas, uint8_t out[32]);
+
+/* One BlockResults response with the trusted header it is checked against. */
+typedef struct {
+  int64_t height;                /* ResultBlockResults.Height */
+  const tmv_tx_result *results;  /* TxsResults */
+  uint32_t n_results;
+  tmv_bytes events;              /* proto.Marshal(ResponseFinalizeBlock{Events: FinalizeBlockEvents}) */
+  tmv_bytes last_results_hash;   /* LastResultsHash of the trusted header at height + 1 */
+} tmv_block_results_in;
+
+/* The checks of the light client's BlockResults after the fetch
+ * (light/rpc/client.go:439-470) for n responses, in its order:
+ *   height must be greater than zero                     (rpc/coretypes/responses.go:20)
+ *   last results %X does not match with trusted last results %X
+ * Items that fail the first check are not hashed.  Results, text layout and
+ * return value as tmv_proof_ops_verify. */
+int tmv_block_results_verify(tmv_ctx *ctx, const tmv_block_results_in *items, uint32_t n, int32_t *results,
+                             char *errs, size_t err_stride);
+
+/* One ConsensusParams response with the trusted header's ConsensusHash. */
+typedef struct {
+  int64_t height;                         /* ResultConsensusParams.BlockHeight */
+  int64_t block_max_bytes, block_max_gas; /* ConsensusParams.Block */
+  tmv_bytes consensus_hash;               /* ConsensusHash of the trusted header at that height */
+} tmv_consensus_params_in;
+
+/* The last two checks of the light client's ConsensusParams
+ * (light/rpc/client.go:274-288) for n responses:
+ *   height must be greater than zero
+ *   params hash %X does not match trusted hash %X
+ * ValidateConsensusParams, which runs before them, stays with the caller.
+ * ctx is unused (every hash is one block, computed on the host).  Results,
+ * text layout and return value as tmv_proof_ops_verify. */
+int tmv_consensus_params_verify(tmv_ctx *ctx, const tmv_consensus_params_in *items, uint32_t n, int32_t *results,
+                                char *errs, size_t err_stride);
+
 #ifdef __cplusplus
 }
 #endif

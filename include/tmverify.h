@@ -240,6 +240,37 @@ int tmv_merkle_roots(tmv_ctx *ctx, const uint8_t *data, const uint32_t *leaf_off
 int tmv_commit_hashes(tmv_ctx *ctx, const uint8_t *flag, const uint8_t *addr_len, const uint8_t *addr,
                       const int64_t *ts_seconds, const int32_t *ts_nanos, const uint8_t *sig_len, const uint8_t *sig,
                       const uint32_t *commit_off, uint32_t n_commits, uint8_t *hash_out);
+/* The hash of a block's ABCI results, for n_trees blocks in one launch:
+ * merkle.HashFromByteSlices over abci.MarshalTxResults (abci/types/types.go:
+ * 213-239), which ApplyBlock stores as State.LastResultsHash
+ * (internal/state/execution.go:262-267) and validateBlock compares with the
+ * next header's LastResultsHash.  Tree t holds the results [tree_off[t],
+ * tree_off[t+1]) (n_trees + 1 offsets, tree_off[0] = 0); result i is code[i],
+ * the data data[data_off[i], data_off[i+1]) (n_results + 1 offsets,
+ * data_off[0] = 0), gas_wanted[i] and gas_used[i].  Its leaf is the gogoproto
+ * encoding of ExecTxResult with fields 1, 2, 5 and 6 alone
+ * (abci/types/types.pb.go:3165-3170): [08 uvarint(code)] [12 uvarint(L) data]
+ * [28 varint(gas_wanted)] [30 varint(gas_used)], zero and empty fields omitted
+ * as proto3 does, a negative gas in the 10-byte two's-complement varint.  Log,
+ * info, events and codespace are not hashed and never come here.
+ * flags: 0, or TMV_RESULTS_FIRST_LEAF: tree t gets the leading leaf
+ * first[first_off[t], first_off[t+1]) (n_trees + 1 offsets; may be empty) in
+ * front of its results -- the light client's proto.Marshal(
+ * ResponseFinalizeBlock{Events}) (light/rpc/client.go:452-464; the reference's
+ * two forms differ, both are as written there).  Without the flag first and
+ * first_off are ignored.
+ * root_out: n_trees x 32 bytes; a tree without leaves hashes to SHA-256("").
+ * One lane hashes one result whatever its length, so one result of many KiB
+ * delays the whole call (the host layer keeps such trees on the host).
+ * TMV_ERR_ARG: null pointers, offsets that do not start at 0 or decrease, an
+ * unknown flag bit, more than 2^26 results or trees, more than 2^30 bytes of
+ * data or of leading leaves.  n_trees == 0 returns 0.  Synchronous, device 0;
+ * 0 or < 0 on error. */
+#define TMV_RESULTS_FIRST_LEAF 1u
+int tmv_tx_results_hashes(tmv_ctx *ctx, uint32_t flags, const uint32_t *code, const int64_t *gas_wanted,
+                          const int64_t *gas_used, const uint8_t *data, const uint32_t *data_off,
+                          const uint32_t *tree_off, uint32_t n_trees, const uint8_t *first, const uint32_t *first_off,
+                          uint8_t *root_out);
 
 /* Merkle inclusion proofs (crypto/merkle/proof.go).  Blocksync's replay loop
  * builds every block's part set (internal/blocksync/reactor.go:563-582:
@@ -355,7 +386,7 @@ int tmv_verify_mixed_batch_ex(tmv_ctx *ctx, uint32_t flags, const uint8_t *kind,
  * "k_secp_verify_comb" (secp256k1 with TMV_FLAG_KEY_CACHE), "k_merkle_leaves_long",
  * "k_merkle_leaves", "k_merkle_tree_levels", "k_merkle_aunts" and "k_merkle_verify_proofs" (the launches
  * of tmv_merkle_proofs / tmv_merkle_verify_proofs), "k_merkle_digests_long" and "k_merkle_value_ops"
- * (tmv_merkle_value_ops), "k_commit_leaves" (tmv_commit_hashes) -- is bracketed by HIP timing events on the stream it runs on
+ * (tmv_merkle_value_ops), "k_commit_leaves" (tmv_commit_hashes), "k_result_leaves" (tmv_tx_results_hashes) -- is bracketed by HIP timing events on the stream it runs on
  * (process-wide, two event records per launch); 0 turns it off.
  * tmv_kernel_timing_read waits for the recorded launches of `kernel`, returns
  * their summed duration and count, and forgets them.  No reference

@@ -39,6 +39,7 @@ TMV_MERKLE_PREHASH = 1
 TMV_MERKLE_LEAF_HASH_GIVEN = 2
 TMV_MERKLE_LONG_LEAVES = 4
 TMV_MERKLE_SHORT_LEAVES = 8
+TMV_RESULTS_FIRST_LEAF = 1
 TMV_KIND_MIXED = 2
 TMV_KIND_SECP256K1 = 3  # include/tmhost.h: 33-byte compressed keys, verified signature by signature
 TMV_VOTE_WITH_BLOCK = 0x80000000
@@ -62,7 +63,7 @@ EXPORTS = [
     "tmv_verify_votes", "tmv_vote_sign_bytes_device", "tmv_verify_votes_and_extensions",
     "tmv_vote_extension_sign_bytes_device", "tmv_merkle_roots",
     "tmv_merkle_aunt_offsets", "tmv_merkle_proofs", "tmv_merkle_verify_proofs", "tmv_merkle_value_ops",
-    "tmv_commit_hashes",
+    "tmv_commit_hashes", "tmv_tx_results_hashes",
     "tmv_kernel_timing", "tmv_kernel_timing_read", "tmv_metrics_read", "tmv_metrics_reset",
     # include/tmhost.h
     "tmv_batch_new", "tmv_batch_add", "tmv_batch_len", "tmv_batch_verify", "tmv_batch_free",
@@ -71,6 +72,7 @@ EXPORTS = [
     "tmv_part_set_headers", "tmv_part_set_proofs", "tmv_parts_verify", "tmv_proofs_verify",
     "tmv_proof_ops_verify", "tmv_tx_proofs_validate",
     "tmv_commit_hash_many", "tmv_blocks_validate_basic",
+    "tmv_results_hash_many", "tmv_consensus_params_hash", "tmv_block_results_verify", "tmv_consensus_params_verify",
     "tmv_vote_extension_sign_bytes", "tmv_vote_extension_template_encode", "tmv_verify_extended_votes",
 ]
 
@@ -208,6 +210,8 @@ def lib() -> ctypes.CDLL:
         L.tmv_merkle_proofs.argtypes = [vp, ctypes.c_uint32, u8p, u32p, ctypes.c_uint32, u32p, ctypes.c_uint32, u8p,
                                         u8p, u32p, u8p]
         i64p = ctypes.POINTER(ctypes.c_int64)
+        L.tmv_tx_results_hashes.argtypes = [vp, ctypes.c_uint32, u32p, i64p, i64p, u8p, u32p, u32p, ctypes.c_uint32,
+                                            u8p, u32p, u8p]
         L.tmv_merkle_verify_proofs.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, i64p, i64p, u8p, u8p, u32p, u8p,
                                                u8p, u32p, i8p, u8p, u8p, u8p]
         L.tmv_merkle_value_ops.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, u8p, u32p, u32p, u8p, u32p, i64p, i64p,
@@ -558,6 +562,37 @@ class Context:
                                                 _p(sig_len), _p(sig), _p(commit_off, ctypes.c_uint32), n_commits,
                                                 _p(out)), "tmv_commit_hashes")
         return out[:n_commits]
+
+    def tx_results_hashes(self, code: np.ndarray, gas_wanted: np.ndarray, gas_used: np.ndarray, data,
+                          data_off: np.ndarray, tree_off: np.ndarray, first=None, first_off=None,
+                          flags=None) -> np.ndarray:
+        """The merkle root over abci.MarshalTxResults of each tree
+        (tmv_tx_results_hashes): (n_trees, 32) uint8.  One entry per result:
+        code, gas_wanted, gas_used and the data data[data_off[i]:data_off[i+1]];
+        tree t holds the results [tree_off[t], tree_off[t+1]).  With `first`
+        (uint8) and `first_off` (n_trees + 1) tree t gets the leading leaf
+        first[first_off[t]:first_off[t+1]] (TMV_RESULTS_FIRST_LEAF; `flags`
+        overrides).  data: uint8 array, or None for a null pointer."""
+        n_trees = len(tree_off) - 1
+        out = np.zeros((max(n_trees, 1), 32), np.uint8)
+
+        def col(a, dtype):
+            a = np.ascontiguousarray(a, dtype)
+            return a if a.size else np.zeros(1, dtype)
+        code, gas_wanted, gas_used = col(code, np.uint32), col(gas_wanted, np.int64), col(gas_used, np.int64)
+        data_off = np.ascontiguousarray(data_off, np.uint32)
+        tree_off = np.ascontiguousarray(tree_off, np.uint32)
+        dp = None if data is None else _p(col(data, np.uint8))
+        fp = None if first is None else _p(col(first, np.uint8))
+        fo = None if first_off is None else np.ascontiguousarray(first_off, np.uint32)
+        if flags is None:
+            flags = TMV_RESULTS_FIRST_LEAF if first_off is not None else 0
+        self._check(self._lib.tmv_tx_results_hashes(self._h, flags, _p(code, ctypes.c_uint32),
+                                                    _p(gas_wanted, ctypes.c_int64), _p(gas_used, ctypes.c_int64), dp,
+                                                    _p(data_off, ctypes.c_uint32), _p(tree_off, ctypes.c_uint32),
+                                                    n_trees, fp, None if fo is None else _p(fo, ctypes.c_uint32),
+                                                    _p(out)), "tmv_tx_results_hashes")
+        return out[:n_trees]
 
     def merkle_roots(self, data, leaf_off: np.ndarray, tree_off: np.ndarray) -> np.ndarray:
         """merkle.HashFromByteSlices of each tree (tmv_merkle_roots): (n_trees, 32) uint8.

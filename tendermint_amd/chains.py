@@ -326,19 +326,28 @@ def blocksync_replay_full(ctx, chain_id: str, vals: H.ValidatorSet, blocks: List
         state.LastBlockID, first.Height-1, first.LastCommit).
     state.LastBlockID is `last_block_id` and state.LastBlockHeight
     `last_block_height` before the first block, and the previous block's
-    afterwards (ApplyBlock).  Left to the caller, because they need
-    application state or the wall clock: Block.Header.Version, AppHash,
-    ConsensusHash and LastResultsHash, the proposer check
-    (Validators.HasAddress), the block time checks, the evidence's own
-    ValidateBasic and its size limit.
+    afterwards (ApplyBlock).  Not checked here, because they need
+    application state: Block.Header.Version, AppHash, ConsensusHash and
+    LastResultsHash, the proposer check (Validators.HasAddress), the block
+    time checks and the evidence size limit -- blocksync_replay_stateful runs
+    them too -- and the evidence's own ValidateBasic.
     `depth` windows in flight (in_order; default 2 on the engine, 1 with a
     caller's `verify_commits`, a function jobs -> per-job error or None);
     `lib`: the host layer to call (the CPU tests pass a build without the
     engine, with ctx = None).  Returns (blocks applied, (height, error) or
     None); the first error is the one the one-at-a-time loop returns."""
+    return _replay_validated(ctx, chain_id, vals, blocks, last_block_id, initial_height, window, depth, part_size,
+                             verify_commits, lib, vals_hash, last_block_height, "blocksync_replay_full")
+
+
+def _replay_validated(ctx, chain_id, vals, blocks, last_block_id, initial_height, window, depth, part_size,
+                      verify_commits, lib, vals_hash, last_block_height, who, stateful=None):
+    """The replay loop of blocksync_replay_full; with `stateful` (a
+    _StatefulChecks) also validateBlock's state-dependent checks, each at its
+    place in the reference's order."""
     for b in blocks[:-1]:
         if b.raw is None:
-            raise ValueError("blocksync_replay_full: block %d has no raw bytes" % b.height)
+            raise ValueError("%s: block %d has no raw bytes" % (who, b.height))
     if depth is None:
         depth = 1 if verify_commits else 2
     if vals_hash is None:
@@ -351,6 +360,7 @@ def blocksync_replay_full(ctx, chain_id: str, vals: H.ValidatorSet, blocks: List
         firsts = blocks[first_of:min(lo + window, len(blocks) - 1)]
         basic = H.blocks_validate_basic(ctx, firsts, lib)
         psh = H.part_set_headers(ctx, [b.raw for b in firsts], part_size, lib)
+        before = stateful.window(ctx, lib, first_of, len(firsts)) if stateful else None
         ids = [H.BlockID(hash_ or b"", total, phash) for (_, hash_), (total, phash) in zip(basic, psh)]
         out, jobs, slots = [], [], []
         for i in range(lo - first_of, len(firsts)):
@@ -360,6 +370,8 @@ def blocksync_replay_full(ctx, chain_id: str, vals: H.ValidatorSet, blocks: List
             state_height = blocks[g - 1].height if g > 0 else last_block_height
             hd = first.header
             err = basic[i][0]
+            if err is None and stateful:
+                err = stateful.version(hd)
             if err is None and hd.chain_id != chain_id:
                 err = "wrong Block.Header.ChainID. Expected %s, got %s" % (chain_id, hd.chain_id)
             if err is None and state_height == 0 and hd.height != initial_height:
@@ -369,6 +381,8 @@ def blocksync_replay_full(ctx, chain_id: str, vals: H.ValidatorSet, blocks: List
             if err is None and not hd.last_block_id.equals(state_last):
                 err = "wrong Block.Header.LastBlockID.  Expected %s, got %s" % (_block_id_string(state_last),
                                                                               _block_id_string(hd.last_block_id))
+            if err is None and stateful:
+                err = stateful.app_info(hd, g, before)
             if err is None and hd.validators_hash != vals_hash:
                 err = "wrong Block.Header.ValidatorsHash.  Expected %s, got %s" % (vals_hash.hex().upper(),
                                                                                  hd.validators_hash.hex().upper())
@@ -386,11 +400,12 @@ def blocksync_replay_full(ctx, chain_id: str, vals: H.ValidatorSet, blocks: List
                     full = len(jobs)
                     jobs.append(H.CommitJob(H.MODE_FULL, chain_id, vals, state_last, hd.height - 1,
                                             first.last_commit))
+            late = stateful.after_commit(first, g) if stateful and err is None else None
             out.append(hd.height)
-            slots.append((light, err, full))
+            slots.append((light, err, full, late))
         res = check(jobs)
-        return [(h, res[light] or err or (res[full] if full is not None else None))
-                for h, (light, err, full) in zip(out, slots)]
+        return [(h, res[light] or err or (res[full] if full is not None else None) or late)
+                for h, (light, err, full, late) in zip(out, slots)]
 
     applied = 0
     for res in in_order(range(0, len(blocks) - 1, window), run, depth):
@@ -399,6 +414,154 @@ def blocksync_replay_full(ctx, chain_id: str, vals: H.ValidatorSet, blocks: List
                 return applied, (height, err)
             applied += 1
     return applied, None
+
+
+@dataclass
+class ReplayState:
+    """The parts of state.State (internal/state/state.go) that validateBlock
+    reads, before the first block of a replay: over a static validator set
+    (Validators == NextValidators == LastValidators) and static consensus
+    params, of which (Block.MaxBytes, Block.MaxGas) are hashed and
+    Evidence.MaxBytes bounds a block's evidence."""
+    chain_id: str
+    validators: H.ValidatorSet
+    app_hash: bytes
+    last_results_hash: bytes
+    last_block_id: H.BlockID = None
+    last_block_height: int = 0
+    last_block_time: Tuple[int, int] = (0, 0)   # the genesis time before the initial block
+    initial_height: int = 1
+    version_block: int = H.BLOCK_PROTOCOL
+    version_app: int = 0
+    block_max_bytes: int = 22020096
+    block_max_gas: int = -1
+    evidence_max_bytes: int = 1048576
+
+
+@dataclass
+class BlockRecord:
+    """What the application answered for one block, as SaveFinalizeBlockResponses
+    stores it: the tx results and the app hash after the block."""
+    results: List[H.TxResult]
+    app_hash: bytes
+
+
+def go_time_string(t: Tuple[int, int]) -> str:
+    """time.Time.String() of a UTC time (seconds, nanos): 2006-01-02
+    15:04:05.999999999 +0000 UTC, the fraction trimmed and absent at zero nanos."""
+    import datetime
+    d = datetime.datetime(1970, 1, 1) + datetime.timedelta(seconds=t[0])
+    frac = ("." + ("%09d" % t[1]).rstrip("0")) if t[1] else ""
+    return "%04d-%02d-%02d %02d:%02d:%02d%s +0000 UTC" % (d.year, d.month, d.day, d.hour, d.minute, d.second, frac)
+
+
+def _uvarint_len(u: int) -> int:
+    n = 1
+    while u >= 0x80:
+        u >>= 7
+        n += 1
+    return n
+
+
+def evidence_byte_size(evidence: List[bytes]) -> int:
+    """EvidenceList.ByteSize (types/evidence.go:593-602): the size of
+    tmproto.EvidenceList over the encoded items, 0 for none."""
+    return sum(1 + _uvarint_len(len(e)) + len(e) for e in evidence)
+
+
+class _StatefulChecks:
+    """validateBlock's checks against state.State (internal/state/validation.go:
+    21-27, 52-71, 98-135) for _replay_validated.  The state before block g is
+    the caller's for g = 0 and follows from block g - 1 and its record
+    afterwards (State.Update with no validator or param changes), so every
+    window is built from inputs alone."""
+
+    def __init__(self, state: ReplayState, blocks, records, lib):
+        if len(records) < len(blocks) - 1:
+            raise ValueError("blocksync_replay_stateful: %d records for %d blocks to apply"
+                             % (len(records), len(blocks) - 1))
+        self.st, self.blocks, self.records = state, blocks, records
+        self.consensus_hash = H.consensus_params_hash(state.block_max_bytes, state.block_max_gas, lib)
+        self.addresses = {v.address for v in state.validators.validators}
+
+    def window(self, ctx, lib, first_of: int, n: int) -> Tuple[int, List[bytes]]:
+        """(first_of, LastResultsHash after each of blocks[first_of : first_of + n - 1]), one call."""
+        lists = [self.records[j].results for j in range(first_of, first_of + n - 1)]
+        return (first_of, H.results_hashes(ctx, lists, None, lib) if lists else [])
+
+    def version(self, hd) -> Optional[str]:
+        st = self.st
+        if hd.version_app != st.version_app or hd.version_block != st.version_block:
+            return "wrong Block.Header.Version. Expected {%d %d}, got {%d %d}" % (
+                st.version_block, st.version_app, hd.version_block, hd.version_app)
+        return None
+
+    def app_info(self, hd, g: int, before) -> Optional[str]:
+        first_of, roots = before
+        app_hash = self.records[g - 1].app_hash if g > 0 else self.st.app_hash
+        results_hash = roots[g - 1 - first_of] if g > 0 else self.st.last_results_hash
+        for name, want, got in (("AppHash", app_hash, hd.app_hash), ("ConsensusHash", self.consensus_hash, hd.consensus_hash),
+                                ("LastResultsHash", results_hash, hd.last_results_hash)):
+            if want != got:
+                return "wrong Block.Header.%s.  Expected %s, got %s" % (name, want.hex().upper(), got.hex().upper())
+        return None
+
+    def after_commit(self, block, g: int) -> Optional[str]:
+        st, hd = self.st, block.header
+        if hd.proposer_address not in self.addresses:
+            return "block.Header.ProposerAddress %s is not a validator" % hd.proposer_address.hex().upper()
+        last_time = self.blocks[g - 1].header.time if g > 0 else st.last_block_time
+        if hd.height > st.initial_height:
+            if not tuple(hd.time) > tuple(last_time):
+                return "block time %s not greater than last block time %s" % (go_time_string(hd.time),
+                                                                              go_time_string(last_time))
+        elif hd.height == st.initial_height:
+            if tuple(hd.time) < tuple(last_time):
+                return "block time %s is before genesis time %s" % (go_time_string(hd.time), go_time_string(last_time))
+        else:
+            return "block height %d lower than initial height %d" % (hd.height, st.initial_height)
+        got = evidence_byte_size(block.evidence)
+        if got > st.evidence_max_bytes:
+            return "Too much evidence: Max %d, got %d" % (st.evidence_max_bytes, got)
+        return None
+
+
+def blocksync_replay_stateful(ctx, state: ReplayState, blocks: List[H.FullBlock], records: List[BlockRecord],
+                              window: int = 600, depth: Optional[int] = None, part_size: int = 65536,
+                              verify_commits=None, lib=None, vals_hash: Optional[bytes] = None
+                              ) -> Tuple[int, Optional[Tuple[int, str]]]:
+    """blocksync_replay_full plus the rest of validateBlock
+    (internal/state/validation.go:14-138): the checks that tie a header to the
+    execution of the block before it, over a static validator set and static
+    consensus params.  records[i] is what the application answered for
+    blocks[i] (SaveFinalizeBlockResponses); after block h the state carries
+    LastResultsHash = the merkle root over records[h].results with no leading
+    leaf (internal/state/execution.go:262-267), AppHash = records[h].app_hash,
+    LastBlockTime = h's time and LastBlockID (State.Update).  Per window all
+    result roots come from one tmv_results_hash_many call beside the window's
+    other launches; HashConsensusParams is computed once.  In the reference's
+    order and with its texts, after VerifyCommitLight of the pair:
+      <Block.ValidateBasic>
+      wrong Block.Header.Version. Expected {B A}, got {B A}
+      wrong Block.Header.ChainID / Height / LastBlockID        (as blocksync_replay_full)
+      wrong Block.Header.AppHash.  Expected %X, got %X
+      wrong Block.Header.ConsensusHash.  Expected %X, got %X
+      wrong Block.Header.LastResultsHash.  Expected %X, got %X
+      wrong Block.Header.ValidatorsHash / NextValidatorsHash   (as blocksync_replay_full)
+      <LastCommit: the initial block's text or VerifyCommit>   (as blocksync_replay_full)
+      block.Header.ProposerAddress %X is not a validator
+      block time %v not greater than last block time %v        (height > initial)
+      block time %v is before genesis time %v                  (height == initial)
+      block height %v lower than initial height %v
+      Too much evidence: Max %d, got %d
+    Times print as Go's time.Time.String() in UTC.  Left to the caller:
+    validator-set and consensus-param updates, the evidence's own verification,
+    ValidateConsensusParams.  The other arguments and the return value are
+    blocksync_replay_full's."""
+    return _replay_validated(ctx, state.chain_id, state.validators, blocks, state.last_block_id or H.BlockID(),
+                             state.initial_height, window, depth, part_size, verify_commits, lib, vals_hash,
+                             state.last_block_height, "blocksync_replay_stateful",
+                             _StatefulChecks(state, blocks, records, lib))
 
 
 # ---- merkle proofs: Txs.Hash / Txs.Proof (types/tx.go:30-75) ----

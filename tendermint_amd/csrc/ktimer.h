@@ -14,8 +14,8 @@ enum Kernel : int {
   kAccum = 0, kWpart = 1, kPrep = 2, kSecpPrep = 3, kSecpVerify = 4,
   kMerkleLeavesLong = 5, kMerkleTreeLevels = 6, kMerkleAunts = 7, kMerkleVerify = 8, kMerkleLeaves = 9,
   kCommitLeaves = 10, kVoteExtSignbytes = 11, kSecpKeyTable = 12, kSecpPrepCached = 13, kSecpVerifyComb = 14,
-  kMerkleDigestsLong = 15, kMerkleValueOps = 16,
-  kCount = 17
+  kMerkleDigestsLong = 15, kMerkleValueOps = 16, kResultLeaves = 17,
+  kCount = 18
 };
 
 void set(bool on);

@@ -1236,3 +1236,159 @@ def blocks_validate_basic(ctx, blocks: List[FullBlock], lib=None) -> List[Tuple[
     Header.Hash of the header as given, which is Block.Hash() of a block that
     passes, or None where the reference returns nil)."""
     return PreparedBlocks(blocks).run(ctx, lib)
+
+
+# ---------------------------------------------------------------- ABCI results and consensus params
+# tmv_results_hash_many / tmv_consensus_params_hash / tmv_block_results_verify /
+# tmv_consensus_params_verify (include/tmhost.h): the merkle root over abci.MarshalTxResults
+# (abci/types/types.go:213-239), HashConsensusParams (types/params.go:385-399) and the checks of the light
+# client's BlockResults and ConsensusParams (light/rpc/client.go:264-291, 420-473).
+
+@dataclass
+class TxResult:
+    """The deterministic fields of abci.ExecTxResult (abci/types/types.go:213-222)."""
+    code: int = 0
+    data: bytes = b""
+    gas_wanted: int = 0
+    gas_used: int = 0
+
+
+@dataclass
+class BlockResults:
+    """coretypes.ResultBlockResults as the light client checks it: events =
+    proto.Marshal(ResponseFinalizeBlock{Events}), last_results_hash = the
+    trusted header's at height + 1."""
+    height: int
+    results: List[TxResult]
+    events: bytes
+    last_results_hash: bytes
+
+
+@dataclass
+class ConsensusParamsResult:
+    """coretypes.ResultConsensusParams' hashed fields with the trusted header's ConsensusHash."""
+    height: int
+    block_max_bytes: int
+    block_max_gas: int
+    consensus_hash: bytes
+
+
+class CTxResult(ctypes.Structure):
+    _fields_ = [("code", ctypes.c_uint32), ("data", CBytes), ("gas_wanted", ctypes.c_int64),
+                ("gas_used", ctypes.c_int64)]
+
+
+class CBlockResultsIn(ctypes.Structure):
+    _fields_ = [("height", ctypes.c_int64), ("results", ctypes.POINTER(CTxResult)), ("n_results", ctypes.c_uint32),
+                ("events", CBytes), ("last_results_hash", CBytes)]
+
+
+class CConsensusParamsIn(ctypes.Structure):
+    _fields_ = [("height", ctypes.c_int64), ("block_max_bytes", ctypes.c_int64), ("block_max_gas", ctypes.c_int64),
+                ("consensus_hash", CBytes)]
+
+
+def _setup_results(L):
+    if not getattr(L, "_tmhost_results", False):
+        i32p = ctypes.POINTER(ctypes.c_int32)
+        L.tmv_results_hash_many.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.POINTER(CTxResult)),
+                                            ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(CBytes), ctypes.c_uint32,
+                                            _u8p]
+        L.tmv_consensus_params_hash.argtypes = [ctypes.c_int64, ctypes.c_int64, _u8p]
+        L.tmv_block_results_verify.argtypes = [ctypes.c_void_p, ctypes.POINTER(CBlockResultsIn), ctypes.c_uint32, i32p,
+                                               ctypes.c_char_p, ctypes.c_size_t]
+        L.tmv_consensus_params_verify.argtypes = [ctypes.c_void_p, ctypes.POINTER(CConsensusParamsIn),
+                                                  ctypes.c_uint32, i32p, ctypes.c_char_p, ctypes.c_size_t]
+        L._tmhost_results = True
+    return L
+
+
+def _c_tx_results(k: _Keep, results: List[TxResult]):
+    arr = (CTxResult * max(1, len(results)))()
+    for j, r in enumerate(results):
+        arr[j] = CTxResult(r.code, _ref_bytes(k, r.data), r.gas_wanted, r.gas_used)
+    k.refs.append(arr)
+    return arr
+
+
+class PreparedResults:
+    """The C arrays of a tmv_results_hash_many call, built once (on the
+    caller's thread; the engine call may run on another)."""
+
+    def __init__(self, lists: List[List[TxResult]], first: Optional[List[bytes]] = None):
+        self.k = k = _Keep()
+        self.n = n = len(lists)
+        self.ptrs = (ctypes.POINTER(CTxResult) * max(1, n))()
+        self.counts = (ctypes.c_uint32 * max(1, n))()
+        for i, rs in enumerate(lists):
+            self.ptrs[i] = ctypes.cast(_c_tx_results(k, rs), ctypes.POINTER(CTxResult))
+            self.counts[i] = len(rs)
+        self.first = None
+        if first is not None:
+            self.first = (CBytes * max(1, n))()
+            for i, b in enumerate(first):
+                self.first[i] = _ref_bytes(k, b)
+        self.out = (ctypes.c_uint8 * (32 * max(1, n)))()
+
+    def run(self, ctx, lib=None) -> List[bytes]:
+        L = _setup_results(lib or _native.lib())
+        rc = L.tmv_results_hash_many(_handle(ctx), self.ptrs, self.counts, self.first, self.n,
+                                     ctypes.cast(self.out, _u8p))
+        if rc < 0:
+            raise NativeError(f"tmv_results_hash_many failed ({rc})")
+        raw = bytes(self.out)
+        return [raw[32 * i:32 * i + 32] for i in range(self.n)]
+
+
+def results_hashes(ctx, lists: List[List[TxResult]], first: Optional[List[bytes]] = None, lib=None) -> List[bytes]:
+    """The merkle root over abci.MarshalTxResults of each list of results:
+    State.LastResultsHash as ApplyBlock stores it.  first: one leading leaf
+    per list (may be empty), the light client's form.  lib: the library to
+    call (default libtmgpu.so; the CPU tests pass the host layer built without
+    the engine, with ctx = None)."""
+    return PreparedResults(lists, first).run(ctx, lib)
+
+
+def consensus_params_hash(block_max_bytes: int, block_max_gas: int, lib=None) -> bytes:
+    """ConsensusParams.HashConsensusParams (types/params.go:385-399)."""
+    L = _setup_results(lib or _native.lib())
+    out = (ctypes.c_uint8 * 32)()
+    rc = L.tmv_consensus_params_hash(block_max_bytes, block_max_gas, ctypes.cast(out, _u8p))
+    if rc < 0:
+        raise NativeError(f"tmv_consensus_params_hash failed ({rc})")
+    return bytes(out)
+
+
+def block_results_verify(ctx, items: List[BlockResults], lib=None) -> List[Optional[str]]:
+    """The checks of the light client's BlockResults after the fetch, for each
+    response: None or the reference's error text."""
+    L = _setup_results(lib or _native.lib())
+    k = _Keep()
+    n = len(items)
+    arr = (CBlockResultsIn * max(1, n))()
+    for i, it in enumerate(items):
+        arr[i] = CBlockResultsIn(it.height, _c_tx_results(k, it.results), len(it.results), _ref_bytes(k, it.events),
+                                 _ref_bytes(k, it.last_results_hash))
+    results = (ctypes.c_int32 * max(1, n))()
+    errs = ctypes.create_string_buffer(ERR_STRIDE * max(1, n))
+    rc = L.tmv_block_results_verify(_handle(ctx), arr, n, results, errs, ERR_STRIDE)
+    if rc < 0:
+        raise NativeError(f"tmv_block_results_verify failed ({rc})")
+    return _texts(results, errs, n)
+
+
+def consensus_params_verify(ctx, items: List[ConsensusParamsResult], lib=None) -> List[Optional[str]]:
+    """The last two checks of the light client's ConsensusParams, for each
+    response: None or the reference's error text."""
+    L = _setup_results(lib or _native.lib())
+    k = _Keep()
+    n = len(items)
+    arr = (CConsensusParamsIn * max(1, n))()
+    for i, it in enumerate(items):
+        arr[i] = CConsensusParamsIn(it.height, it.block_max_bytes, it.block_max_gas, _ref_bytes(k, it.consensus_hash))
+    results = (ctypes.c_int32 * max(1, n))()
+    errs = ctypes.create_string_buffer(ERR_STRIDE * max(1, n))
+    rc = L.tmv_consensus_params_verify(_handle(ctx), arr, n, results, errs, ERR_STRIDE)
+    if rc < 0:
+        raise NativeError(f"tmv_consensus_params_verify failed ({rc})")
+    return _texts(results, errs, n)
