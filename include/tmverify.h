@@ -421,6 +421,11 @@ int tmv_bucket_entry_stats(tmv_ctx *ctx, uint64_t *entries);
  * only; the caller has waited for the launches it wants counted. */
 int tmv_group_fail_stats(tmv_ctx *ctx, uint64_t *groups_failed, uint64_t *groups_located, uint64_t *fallback_entries);
 
+/* Split key scalars of the same launches: groups whose A and B scalars were
+ * split into a low and a high half, and the leaders' high points computed
+ * for them.  Counted and read as tmv_group_fail_stats. */
+int tmv_split_stats(tmv_ctx *ctx, uint64_t *groups_split, uint64_t *high_points);
+
 /* Library metrics (verifies/s, batch size, fallback count, H2D
  * bytes -- the reference exports its own per package through Prometheus,
  * e.g. internal/consensus/metrics.gen.go; a Go shim would publish these).

@@ -57,6 +57,7 @@ EXPORTS = [
     "tmv_secp256k1_key_cache_stats",
     "tmv_verify_mixed_batch", "tmv_ed25519_verify_batch_device", "tmv_verify_mixed_batch_device",
     "tmv_verify_batch_ex", "tmv_key_cache_stats", "tmv_point_cache_stats", "tmv_bucket_entry_stats", "tmv_group_fail_stats",
+    "tmv_split_stats",
     "tmv_set_batch_options", "tmv_batch_stats",
     "tmv_subgroup_stats", "tmv_validator_set_hashes",
     "tmv_verify_mixed_batch_ex", "tmv_verify_batch_device_ex", "tmv_verify_batches_device",
@@ -194,6 +195,7 @@ def lib() -> ctypes.CDLL:
                                             ctypes.POINTER(ctypes.c_uint32)]
         L.tmv_bucket_entry_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
         L.tmv_group_fail_stats.argtypes = [vp] + [ctypes.POINTER(ctypes.c_uint64)] * 3
+        L.tmv_split_stats.argtypes = [vp] + [ctypes.POINTER(ctypes.c_uint64)] * 2
         L.tmv_set_batch_options.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, u8p, ctypes.c_uint32]
         L.tmv_batch_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
         L.tmv_kernel_timing.argtypes = [vp, ctypes.c_int]
@@ -751,6 +753,12 @@ class Context:
         self._check(self._lib.tmv_group_fail_stats(self._h, ctypes.byref(f), ctypes.byref(l), ctypes.byref(e)),
                     "tmv_group_fail_stats")
         return {"failed": f.value, "located": l.value, "fallback_entries": e.value}
+
+    def split_stats(self) -> dict:
+        """Split groups and high points computed of the stats launches (read from the devices now)."""
+        g, h = ctypes.c_uint64(), ctypes.c_uint64()
+        self._check(self._lib.tmv_split_stats(self._h, ctypes.byref(g), ctypes.byref(h)), "tmv_split_stats")
+        return {"groups_split": g.value, "high_points": h.value}
 
     def metrics(self) -> dict:
         """tmv_metrics: cumulative counters (plus verifies_per_s_host, the

@@ -50,6 +50,32 @@
 // out of the sums stay out, and a run's first entry is always a live one.
 // sr25519, mixed launches and the key-merged form below are not merged here.
 //
+// Split key scalars (split.h; launches that merge runs, one running-sum lane
+// per window, kMsmSplitGroups groups or more): after merging, a group of
+// column-ordered slots holds a few 254-bit scalars (its leaders' A terms and
+// the B term) among m 128-bit R weights, so windows WR..W-1 hold a handful of
+// entries and still cost k_msm_wpart a full running sum and k_msm_horner c
+// doublings each.  With Ws = ceil(W / 2),
+//   [a]P = [a mod 2^(c Ws)]P + [a >> (c Ws)]([2^(c Ws)]P),
+// which in signed digits is a relabelling: digit d_w, w >= Ws, becomes the
+// entry (window w - Ws, P_hi = [2^(c Ws)]P).  A group with at most
+// p.split_max leaders is sorted that way and then fills only windows
+// [0, max(Ws, WR)) ([0, max(Ws, WL)) in the located pass):
+//   k_msm_sort      counts the leaders, decides, ranks them by entry index
+//                   (slot = group x split_max + rank), lists (leader, slot)
+//   k_msm_hi_points one quad per listed leader: c Ws doublings of its -A,
+//                   back to the affine Niels line at pts[2n + 2 + slot];
+//                   pts[2n + 1] = [2^(c Ws)]B is a constant of the context
+//   k_msm_wpart     windows [0, Wa) of every group, the rest of the unsplit
+//                   groups only (mw.uns_list)
+//   k_msm_horner    a split group starts at window Wa - 1
+// Why the validity vector stays what it was: the identity holds for every
+// point and scalar, so T_g is the same group element EXACTLY (not only up to
+// torsion); the digits and their count are the same; the verdict, the located
+// search, the false-accept bound and the fallback (which reads each entry's
+// own -A, never a high point) see no difference.  High points live for one
+// launch: a cached one could not be checked cheaply.
+//
 // Key-merged form (batches whose keys sit in the
 // device key cache, e.g. commits of one validator set): entries are ordered
 // by key, so a group holds few distinct keys, and the A terms collapse to
@@ -64,8 +90,10 @@
 //   k_msm_horner<KM> Horner over the R windows + the group's item points
 // The per-entry fallback of failing groups is the key-cached comb kernel.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 #include "curve25519.h"
+#include "split.h"
 
 namespace tmv {
 
@@ -73,6 +101,14 @@ constexpr uint32_t kMsmWideRows = 65536;     // (group, window) rows from which 
 constexpr int kMsmChunkMax = 32;             // sorted entries per accumulation lane: 16 or 32
 constexpr uint32_t kMsmEmpty = 0xffffffffu;  // padding entry / no bucket
 constexpr uint32_t kMsmCompactGroups = 2048; // groups from which k_msm_accum's lanes cover the live chunks only
+// Groups from which merged key scalars are split (split.h; with P == 1).  The
+// high points are a chain of c Ws doublings and an inversion in front of the
+// bucket sums (~0.25 ms whatever the size): single launches alone, groups of
+// 128, split off -> on: 2,500 groups 2.33 -> 2.55 ms, 5,000 groups 3.84 ->
+// 3.57, 10,000 groups 6.57 -> 6.34, 20,000 groups 12.61 -> 12.34
+// (profiles/scalar_split/split_max.txt, split_size.txt).
+constexpr uint32_t kMsmSplitGroups = 4096;
+constexpr uint32_t kMsmSplitMax = 8;         // most leaders a group may have and still split
 constexpr int kMsmSortBlock = 256;
 // Buckets cut by chunk edges are joined by k_msm_accum (neighbouring lanes of
 // a wave) and k_msm_join_list (the rest, from a packed list) before the
@@ -127,6 +163,12 @@ struct MsmParams {
   uint32_t L;        // sorted entries per k_msm_accum lane (16 or 32)
   uint32_t merged;   // key-merged form: R points only, W = WR
   uint32_t sub;      // 1: sub-group bisection (k_msm_subcheck) of failing groups; set by the runtime
+  // split key scalars (split.h; set by the runtime on launches that merge runs)
+  uint32_t Ws;         // windows of a scalar's low half: ceil(W / 2)
+  uint32_t Wa;         // windows a split group uses in the primary pass: max(Ws, WR)
+  uint32_t Wl;         // ... in the located pass: max(Ws, WL())
+  uint32_t split_max;  // most leaders (non-zero A scalars) a group may have and still split
+  uint32_t split;      // 1: groups of at most split_max leaders split their A and B scalars
 
   TMV_HD uint32_t m() const { return 1u << m_log2; }
   // windows of the located pass's R weights z (j + 1) < 2^(128 + m_log2)
@@ -187,13 +229,19 @@ struct MsmParams {
     // lanes' T, so k_msm_wsum is skipped.  C2 bench: 82.9 / 84.1 (P = 4) ->
     // 85.0 / 86.2 M/s (P = 1), profiles/r03/ab_parts.txt
     if ((uint64_t)p.groups * p.W >= kMsmWideRows) p.P = 1;
+    p.Ws = split_windows(p.W);
+    p.Wa = p.Ws > p.WR ? p.Ws : p.WR;
+    p.Wl = p.Ws > p.WL() ? p.Ws : p.WL();
+    p.split_max = 0;
+    p.split = 0;
     return p;
   }
 };
 
 // Device workspace of the batch check (all per launch stream).
 struct MsmWork {
-  niels_pt *pts;       // points 2n+1: [2e] = -R_e, [2e+1] = -A_e, [2n] = B; kNielsPer slots each
+  niels_pt *pts;       // points: [2e] = -R_e, [2e+1] = -A_e, [2n] = B; split launches: [2n+1] = [2^(c Ws)]B,
+                       // [2n+2 + g split_max + r] = high point of group g's leader of rank r; kNielsPer slots each
   uint32_t *ent_pt;    // groups x cap: point index << 1 | negate
   uint32_t *ent_bk;    // groups x cap: global bucket id, kMsmEmpty for padding
   uint32_t *bk_start;  // groups x W x H: first sorted slot of the bucket
@@ -236,7 +284,17 @@ struct MsmWork {
   // merging; and the device's count of bucket entries sorted (null: not
   // counted).  Both are set by the launch, not by carve.
   const uint8_t *merge_pk;
-  unsigned long long *ent_total;  // [0] entries sorted, [1] failing groups, [2] located groups, [3] entries left one by one
+  // split key scalars (split.h; null unless p.split).  The lists' counters are
+  // per part view, as join_count: parts of one launch run at once.
+  uint8_t *grp_split;   // 2 x groups: [g] group g is split, [groups + f] the located pass's slot f
+  uint32_t *hi_of;      // n: slot (g split_max + rank, launch-wide) of entry e's high point, kMsmEmpty = none
+  uint32_t *hi_list;    // groups x split_max pairs (leader entry, slot): the high points k_msm_hi_points computes
+  uint32_t *uns_list;   // groups: the unsplit groups (located pass: slots), for k_msm_wpart's second lane range
+  uint32_t *split_cnt;  // 2 x groups: [2 g0] counts hi_list, [2 g0 + 1] uns_list of the view starting at group g0;
+                        // zeroed before every k_msm_sort launch
+  uint32_t g_base;      // launch-wide index of the view's first group
+  unsigned long long *ent_total;  // [0] entries sorted, [1] failing groups, [2] located groups, [3] entries left one by one,
+                                  // [4] split groups, [5] high points computed
   // key-merged form only (null otherwise)
   uint32_t *wscal;     // n x 8 words: z_e k_e mod l (0 for entries left out)
   uint32_t *bscal;     // groups x 8 words: B scalar of the group
@@ -245,15 +303,20 @@ struct MsmWork {
   // item capacity of the key-merged form: runs (<= n + groups) + groups
   static size_t max_items(uint32_t n, const MsmParams &p) { return (size_t)n + 2ull * p.groups; }
 
+  // point slots: 2n + 1, and on split launches [2^(c Ws)]B and the leaders' high points
+  static size_t point_slots(uint32_t n, const MsmParams &p) {
+    return 2ull * n + 1 + (p.split ? 1 + (size_t)p.groups * p.split_max : 0);
+  }
   static size_t bytes(uint32_t n, const MsmParams &p) {
     const size_t G = p.groups, bk = (size_t)G * p.buckets_per_group(), ent = (size_t)G * p.cap;
     const size_t chunks = ent / p.L;
-    size_t b = (2ull * n + 1) * kNielsPer * sizeof(niels_pt) + 8 * ent + 8 * bk + bk * sizeof(ge_p3) +
+    size_t b = point_slots(n, p) * kNielsPer * sizeof(niels_pt) + 8 * ent + 8 * bk + bk * sizeof(ge_p3) +
                2 * chunks * sizeof(ge_p3) + 4 * chunks + G * p.W * (2ull * p.wpart_slots() + 1) * sizeof(ge_p3) + G + 2 * G +
                18 * 16 + 4 * G + 8 * G + 32;
     if (p.merged) b += 32ull * n + 32 * G + max_items(n, p) * 4 * sizeof(fe);
     else b += 16 + 4 * G + (G << p.m_log2) / kSubGroup + 16 + (size_t)n * 32 * sizeof(fe) + 3 * 16 +
               G * 8 * sizeof(fe) + 16 + 4ull * n + 2 * 16 + 4 * G + 2 * 16 + G * 4 * sizeof(fe) + 16;
+    if (p.split) b += 2 * G + 4ull * n + 8 * G * p.split_max + 4 * G + 8 * G + 5 * 16;
     return b;
   }
   static MsmWork carve(void *base, uint32_t n, const MsmParams &p) {
@@ -263,7 +326,7 @@ struct MsmWork {
     const size_t chunks = ent / p.L;
     MsmWork w;
     size_t o = 0;
-    w.pts = reinterpret_cast<niels_pt *>(b + o); o = up(o + (2ull * n + 1) * kNielsPer * sizeof(niels_pt));
+    w.pts = reinterpret_cast<niels_pt *>(b + o); o = up(o + point_slots(n, p) * kNielsPer * sizeof(niels_pt));
     w.ent_pt = reinterpret_cast<uint32_t *>(b + o); o = up(o + 4 * ent);
     w.ent_bk = reinterpret_cast<uint32_t *>(b + o); o = up(o + 4 * ent);
     w.bk_start = reinterpret_cast<uint32_t *>(b + o); o = up(o + 4 * bk);
@@ -281,6 +344,9 @@ struct MsmWork {
     w.sort_ovf = b + o; o = up(o + 2 * G);
     w.n_pts = 2 * n;
     w.merge_pk = nullptr;
+    w.grp_split = nullptr;
+    w.hi_of = w.hi_list = w.uns_list = w.split_cnt = nullptr;
+    w.g_base = 0;
     w.compact = 0;
     w.ent_total = nullptr;
     w.wscal = w.bscal = nullptr;
@@ -306,6 +372,13 @@ struct MsmWork {
       w.wscal = reinterpret_cast<uint32_t *>(b + o); o = up(o + 32ull * n);
       w.bscal = reinterpret_cast<uint32_t *>(b + o); o = up(o + 32 * G);
       w.item_pt = reinterpret_cast<fe *>(b + o);
+    }
+    if (p.split) {
+      w.grp_split = b + o; o = up(o + 2 * G);
+      w.hi_of = reinterpret_cast<uint32_t *>(b + o); o = up(o + 4ull * n);
+      w.hi_list = reinterpret_cast<uint32_t *>(b + o); o = up(o + 8 * G * p.split_max);
+      w.uns_list = reinterpret_cast<uint32_t *>(b + o); o = up(o + 4 * G);
+      w.split_cnt = reinterpret_cast<uint32_t *>(b + o); o = up(o + 8 * G);
     }
     return w;
   }

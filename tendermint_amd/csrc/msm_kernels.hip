@@ -169,6 +169,19 @@ __device__ __forceinline__ void p3_add(ge_p3 &a, const ge_p3 &b) {
 // groups merge their first 256 runs.
 TMV_HD uint32_t merge_runs(const MsmParams &p) { return p.m() / 2 < 256u ? p.m() / 2 : 256u; }
 
+// Words of k_msm_sort's dynamic LDS: the bucket counters / cursors, then the
+// scalar reduction, the scan and one window's staged entries (point, bucket),
+// or the run merge's tables, which alias everything behind the histogram
+// (3 x 2m table words, a counter, 16 limbs per run).  The SPLIT sort keeps
+// kSplitWords more behind them: one bit per entry (leaders), the group's
+// leader count and the base of its leaders in the high-point list.
+constexpr uint32_t kSplitWords = 40;
+TMV_HD uint32_t sort_words(const MsmParams &p, uint32_t bs) {
+  const uint32_t sort = bs * 9 + bs + 1 + 2 * (2 * p.m() + 1);
+  const uint32_t merge = 6 * p.m() + 1 + 16 * merge_runs(p);
+  return p.W * p.H + (sort > merge ? sort : merge);
+}
+
 __device__ __forceinline__ void p3_dbl(ge_p3 &a) {
   ge_p1p1 r;
   ge_p3_dbl(r, a);
@@ -187,7 +200,16 @@ __device__ __forceinline__ void p3_dbl(ge_p3 &a) {
 // index in its group, so the same bucket stages compute
 // T'_f = sum (j+1) z_j Delta_j (z_j (j+1) < 2^(128 + m_log2): p.WL() R
 // windows).
-template <bool SR, bool KM, int BS = kMsmSortBlock, bool LOC = false>
+// SPLIT (split.h; launches with p.split that merge runs): after the merge step
+// the group counts its leaders -- live entries whose A scalar is not zero --
+// and, with at most p.split_max of them, relabels the digits of windows
+// >= p.Ws of its A and B scalars to (window - p.Ws, high point), so that it
+// fills only windows [0, p.Wa) (LOC: p.Wl).  A leader's high point has the
+// slot (group, rank by entry index); the primary pass writes the slots to
+// mw.hi_of and lists them for k_msm_hi_points, the LOC pass reads the primary
+// pass's decision and slots.  Every other group keeps all W windows and lists
+// itself for k_msm_wpart's second lane range.
+template <bool SR, bool KM, int BS = kMsmSortBlock, bool LOC = false, bool SPLIT = false>
 __global__ void __launch_bounds__(BS)
 k_msm_sort(const uint8_t *__restrict__ sig, const uint32_t *__restrict__ idx, const uint32_t *count_ptr, uint32_t n,
            Ed25519Work w, MsmWork mw, MsmParams p, MsmSeed seed, const fe *__restrict__ btab_q, int aligned,
@@ -217,6 +239,13 @@ k_msm_sort(const uint8_t *__restrict__ sig, const uint32_t *__restrict__ idx, co
     bp.xy2d = btab_q[2];
     bp.pad[0] = bp.pad[1] = 0;
     niels_store(mw.pts, mw.n_pts, bp);
+    if constexpr (SPLIT) {  // [2^(c Ws)]B: the table's entry for this window size (tmverify_runtime.cpp)
+      const fe *bh = btab_q + 4 * (2 * kBaseQuadEntries + (p.c - 4));
+      bp.ymx = bh[0];
+      bp.ypx = bh[1];
+      bp.xy2d = bh[2];
+      niels_store(mw.pts, mw.n_pts + 1, bp);
+    }
     if (mw.fail_count) *mw.fail_count = 0;  // k_msm_horner appends the failing groups
   }
   if (e0 >= cnt) return;  // block-uniform
@@ -467,14 +496,98 @@ k_msm_sort(const uint8_t *__restrict__ sig, const uint32_t *__restrict__ idx, co
     }
   }
 
+  // Split key scalars (split.h): the group's leaders, its decision and the
+  // leaders' high-point slots.
+  bool split_g = false;            // block-uniform
+  uint32_t hi_pt[R];               // point index of entry r's high point
+  int carry_hi[R], carry_bhi = 0;  // the recoding's carry into window Ws (pass 1 hands it to pass 2)
+  uint32_t *lmask = smem + sort_words(p, BS), *lbad = lmask + 32, *lbase = lmask + 33;
+  if constexpr (SPLIT) {
+    bool lead[R];
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+      hi_pt[r] = 0;
+      carry_hi[r] = 0;
+      uint32_t nz = 0;
+#pragma unroll
+      for (int t = 0; t < 8; t++) nz |= wv[r][t];
+      lead[r] = live[r] && nz != 0;
+    }
+    if (tid < 34) lmask[tid] = 0;
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+      const uint32_t j = tid + r * BS;
+      if (lead[r]) atomicOr(&lmask[j >> 5], 1u << (j & 31));
+    }
+    __syncthreads();
+    uint32_t leaders = 0;
+    for (uint32_t k = 0; k < (p.m() + 31) / 32; k++) leaders += __popc(lmask[k]);
+    // the located pass takes the primary pass's decision (the same live set
+    // and the same leaders)
+    split_g = LOC ? mw.grp_split[g] != 0 : leaders <= p.split_max;
+    if (tid == 0) {
+      mw.grp_split[(LOC ? p.groups : 0) + slot] = split_g ? 1 : 0;
+      if (!split_g) {
+        mw.uns_list[atomicAdd(&mw.split_cnt[1], 1u)] = slot;
+      } else if (!LOC) {
+        *lbase = atomicAdd(&mw.split_cnt[0], leaders);
+        if (mw.ent_total) {
+          atomicAdd(&mw.ent_total[4], 1ull);
+          atomicAdd(&mw.ent_total[5], (unsigned long long)leaders);
+        }
+      }
+    }
+    if (split_g) {  // block-uniform
+      if (!LOC) __syncthreads();
+#pragma unroll
+      for (int r = 0; r < R; r++) {
+        if (!live[r]) continue;
+        const uint32_t j = tid + r * BS, e = e0 + j;
+        uint32_t gslot = kMsmEmpty;
+        if (LOC) {
+          if (lead[r]) {
+            gslot = mw.hi_of[e];
+            if (gslot == kMsmEmpty) atomicOr(lbad, 1u);  // cannot happen; the group fails closed below
+          }
+        } else {
+          if (lead[r]) {
+            uint32_t rank = __popc(lmask[j >> 5] & ((1u << (j & 31)) - 1));
+            for (uint32_t k = 0; k < (j >> 5); k++) rank += __popc(lmask[k]);
+            gslot = (mw.g_base + g) * p.split_max + rank;
+            mw.hi_list[2 * (*lbase + rank)] = e;
+            mw.hi_list[2 * (*lbase + rank) + 1] = gslot;
+          }
+          mw.hi_of[e] = gslot;
+        }
+        hi_pt[r] = mw.n_pts + 2 + gslot;
+      }
+    }
+  }
+  // SPLIT, pass 1: the digits of an A or B scalar, relabelled in a split group
+  auto count_split = [&](const uint32_t *s, int &cy) {
+    DigitReader<8> rd;
+    rd.init(s);
+    for (uint32_t w = 0; w < p.W; w++) {
+      if (w == p.Ws) cy = rd.carry;
+      const int d = rd.next(p.c, w + 1 == p.W);
+      if (d != 0) atomicAdd(&hist[p.bucket(split_slot(w, p.Ws, split_g).window, (uint32_t)((d < 0 ? -d : d) - 1))], 1u);
+    }
+  };
+
   // pass 1: bucket sizes
 #pragma unroll
   for (int r = 0; r < R; r++) {
     if (!live[r]) continue;
     for_each_digit<ZW>(z[r], WRz, p, [&](uint32_t bk, bool) { atomicAdd(&hist[bk], 1u); });
-    if (!KM) for_each_digit<8>(wv[r], p.W, p, [&](uint32_t bk, bool) { atomicAdd(&hist[bk], 1u); });
+    if constexpr (SPLIT) count_split(wv[r], carry_hi[r]);
+    else if (!KM) for_each_digit<8>(wv[r], p.W, p, [&](uint32_t bk, bool) { atomicAdd(&hist[bk], 1u); });
   }
-  if (!KM && tid == 0) for_each_digit<8>(bsc, p.W, p, [&](uint32_t bk, bool) { atomicAdd(&hist[bk], 1u); });
+  if constexpr (SPLIT) {
+    if (tid == 0) count_split(bsc, carry_bhi);
+  } else {
+    if (!KM && tid == 0) for_each_digit<8>(bsc, p.W, p, [&](uint32_t bk, bool) { atomicAdd(&hist[bk], 1u); });
+  }
   __syncthreads();
 
   // exclusive scan: contiguous segments per thread, thread 0 scans the totals
@@ -499,7 +612,7 @@ k_msm_sort(const uint8_t *__restrict__ sig, const uint32_t *__restrict__ idx, co
   // more entries than slots cannot happen (MsmParams::make sizes cap by the
   // digits that can occur); if it did, leave the group empty and flag it so
   // k_msm_horner / k_loc_search fail it -- never a wrong sum
-  const bool ovf = scan[BS] > p.cap;  // block-uniform
+  const bool ovf = scan[BS] > p.cap || (SPLIT && *lbad != 0);  // block-uniform
   if (tid == 0) mw.sort_ovf[(LOC ? p.groups : 0) + slot] = ovf ? 1 : 0;
   if (tid == 0 && !ovf && mw.ent_total) atomicAdd(mw.ent_total, (unsigned long long)scan[BS]);
   if (tid == 0) mw.grp_chunks[slot] = ovf ? 0u : (scan[BS] + p.L - 1) / p.L;  // k_msm_chunk_scan's input
@@ -533,6 +646,75 @@ k_msm_sort(const uint8_t *__restrict__ sig, const uint32_t *__restrict__ idx, co
   const uint32_t wcap = 2 * p.m() + 1;  // entries one window can hold: m R + m A digits + B
   uint32_t *st_pt = scan + BS + 1, *st_bk = st_pt + wcap;
   DigitReader<ZW> rz[R];
+  const uint32_t total = scan[BS];
+  if constexpr (SPLIT) {
+    // Every A and B scalar is read as its low half (windows [0, Ws), at most
+    // 160 bits) and its high half (the scalar >> c Ws, below 2^128, entered
+    // with pass 1's carry).  A split group steps both halves in one window
+    // loop over [0, Wa); an unsplit group reads the low half, then the high
+    // one, over all W windows.
+    DigitReader<5> rlo[R], rblo;
+    DigitReader<4> rhi[R], rbhi;
+    const uint32_t sh = p.c * p.Ws;
+    auto high_half = [&](DigitReader<4> &rd, const uint32_t *s, int cy) {
+      uint32_t t[9], h[4];
+#pragma unroll
+      for (int k = 0; k < 8; k++) t[k] = s[k];
+      t[8] = 0;
+      for (uint32_t i = 0; i < (sh >> 5); i++) {
+#pragma unroll
+        for (int k = 0; k < 8; k++) t[k] = t[k + 1];
+      }
+#pragma unroll
+      for (int k = 0; k < 4; k++) h[k] = (uint32_t)((((uint64_t)t[k + 1] << 32) | t[k]) >> (sh & 31));
+      rd.init(h);
+      rd.carry = cy;
+    };
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+      rz[r].init(z[r]);
+      rlo[r].init(wv[r]);
+      high_half(rhi[r], wv[r], carry_hi[r]);
+    }
+    rblo.init(bsc);
+    high_half(rbhi, bsc, carry_bhi);
+    const uint32_t Wg = split_g ? (LOC ? p.Wl : p.Wa) : p.W;
+    for (uint32_t w = 0; w < Wg; w++) {
+      const uint32_t wbeg = hist[p.bucket(w, 0)];
+      const uint32_t wend = w + 1 < p.W ? hist[p.bucket(w + 1, 0)] : total;
+      __syncthreads();  // bounds read (and the previous window stored) before the cursors move
+      auto put = [&](int d, uint32_t pt) {
+        if (d == 0) return;
+        const uint32_t bk = p.bucket(w, (uint32_t)((d < 0 ? -d : d) - 1));
+        const uint32_t pos = atomicAdd(&hist[bk], 1u) - wbeg;  // < cap: checked above
+        st_pt[pos] = (pt << 1) | (d < 0 ? 1u : 0u);
+        st_bk[pos] = bbase + bk;
+      };
+      // the window of the scalars' high halves that lands in bucket window w
+      const uint32_t wh = split_g ? w + p.Ws : w;
+      const bool lo_on = w < p.Ws, hi_on = wh >= p.Ws && wh < p.W;
+#pragma unroll
+      for (int r = 0; r < R; r++) {
+        if (!live[r]) continue;
+        const uint32_t e = e0 + tid + r * BS;
+        if (w < WRz) put(rz[r].next(p.c, w + 1 == WRz), 2 * e);
+        if (lo_on) put(rlo[r].next(p.c, false), 2 * e + 1);
+        if (hi_on) put(rhi[r].next(p.c, wh + 1 == p.W), split_g ? hi_pt[r] : 2 * e + 1);
+      }
+      if (tid == 0) {
+        if (lo_on) put(rblo.next(p.c, false), mw.n_pts);
+        if (hi_on) put(rbhi.next(p.c, wh + 1 == p.W), split_g ? mw.n_pts + 1 : mw.n_pts);
+      }
+      __syncthreads();
+      for (uint32_t i = tid; i < wend - wbeg; i += BS) {
+        ent_pt[wbeg + i] = st_pt[i];
+        ent_bk[wbeg + i] = st_bk[i];
+      }
+    }
+    const uint32_t pad_end = mw.compact ? min(p.cap, (total + p.L - 1) / p.L * p.L) : p.cap;
+    for (uint32_t t = total + tid; t < pad_end; t += BS) ent_bk[t] = kMsmEmpty;
+    return;
+  }
   DigitReader<8> rw[R], rb;
 #pragma unroll
   for (int r = 0; r < R; r++) {
@@ -540,7 +722,6 @@ k_msm_sort(const uint8_t *__restrict__ sig, const uint32_t *__restrict__ idx, co
     rw[r].init(wv[r]);
   }
   rb.init(bsc);
-  const uint32_t total = scan[BS];
   for (uint32_t w = 0; w < p.W; w++) {
     const uint32_t wbeg = hist[p.bucket(w, 0)];
     const uint32_t wend = w + 1 < p.W ? hist[p.bucket(w + 1, 0)] : total;
@@ -587,6 +768,55 @@ k_msm_sort(const uint8_t *__restrict__ sig, const uint32_t *__restrict__ idx, co
   // reads the live chunks only (mw.compact), to the end of the last of them
   const uint32_t pad_end = mw.compact ? min(p.cap, (total + p.L - 1) / p.L * p.L) : p.cap;
   for (uint32_t t = total + tid; t < pad_end; t += BS) ent_bk[t] = kMsmEmpty;
+}
+
+// High points of the split groups' leaders (split.h): one quad per pair
+// (leader entry e, slot) of the primary sort's list, 64 pairs a workgroup.
+// P_hi = [2^(c Ws)](-A_e) by c Ws doublings of the entry's own -A
+// (Ed25519Work::negA, P3Q), then affine and stored as the Niels line
+// k_msm_accum loads.  The inversions take one lane per point: the quads leave
+// their Z in LDS and the workgroup's first wave inverts all 64 (inverted by
+// its own four lanes, a quad would spend as long on one Z as on the 130
+// doublings).  The doubling and the inversion are complete: a small-order
+// key's high point is a torsion point or the identity (Z never 0) like any
+// other.  The grid covers every group splitting with split_max leaders;
+// blocks past the list's count exit at once.
+constexpr int kHiBlock = 256;
+__global__ void __launch_bounds__(kHiBlock)
+k_msm_hi_points(Ed25519Work w, MsmWork mw, MsmParams p) {
+  constexpr uint32_t kPts = kHiBlock / 4;
+  __shared__ fe zs[kPts];
+  const uint32_t cnt = mw.split_cnt[0];
+  if (blockIdx.x * kPts >= cnt) return;  // block-uniform
+  const uint32_t q = threadIdx.x >> 2, raw = blockIdx.x * kPts + q;
+  const bool live = raw < cnt;
+  const uint32_t i = live ? raw : cnt - 1;  // whole quads stay active for DPP
+  const int c = (int)(threadIdx.x & 3);
+  const uint32_t e = mw.hi_list[2 * i], gslot = mw.hi_list[2 * i + 1];
+  fe acc = w.negA[4ull * e + c], r;
+  for (uint32_t d = 0; d < p.c * p.Ws; d++) {
+    quad::dbl(r, acc);
+    quad::p1p1_to_p3(acc, r);
+  }
+  if (c == 2) zs[q] = acc;
+  __syncthreads();
+  if (threadIdx.x < kPts) {
+    fe zi;
+    fe_invert(zi, zs[threadIdx.x]);
+    zs[threadIdx.x] = zi;
+  }
+  __syncthreads();
+  fe a, x, y, t, u;
+  fe_mul(a, acc, zs[q]);  // (x, y, 1, x y)
+  quad::fe_dpp<quad::qp(0, 0, 0, 0)>(x, a);
+  quad::fe_dpp<quad::qp(1, 1, 1, 1)>(y, a);
+  quad::fe_dpp<quad::qp(3, 3, 3, 3)>(t, a);
+  niels_pt np;
+  fe_add(u, y, x); fe_carry(np.ypx, u);
+  fe_sub(u, y, x); fe_carry(np.ymx, u);
+  fe_mul(np.xy2d, t, consts::d2());
+  np.pad[0] = np.pad[1] = 0;
+  if (live && c == 0) niels_store(mw.pts, (uint64_t)mw.n_pts + 2 + gslot, np);
 }
 
 #ifdef TMV_CHECKS
@@ -857,13 +1087,38 @@ __device__ __forceinline__ void store_window_sum(ge_p3 *dst, const ge_p3 &S, boo
 // window (P = 1) keeps U in cached form only: U += B adds the P3 bucket sum
 // to the cached U and converts the result straight back, T += U takes that
 // cached U -- 17 multiplications a bucket instead of 18.
+//
+// Split launches (gsplit: the pass's half of mw.grp_split; P = 1): two dense
+// lane ranges.  Lanes [0, groups x wa) cover windows [0, wa) of every group;
+// the blocks behind them cover windows [wa, W) of the unsplit groups only,
+// through mw.uns_list, and exit at once past its count -- a split group has
+// no entries there, and no lane waits on one.
 __global__ void __launch_bounds__(256)
-k_msm_wpart(const uint32_t *count_ptr, uint32_t n, MsmWork mw, MsmParams p) {
-  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+k_msm_wpart(const uint32_t *count_ptr, uint32_t n, MsmWork mw, MsmParams p, const uint8_t *__restrict__ gsplit,
+            uint32_t wa) {
+  uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t per_group = p.W * p.P;
-  const uint32_t g = t / per_group;
+  uint32_t g, r;
+  if (gsplit) {
+    const uint32_t b1 = (p.groups * wa + blockDim.x - 1) / blockDim.x;
+    if (blockIdx.x < b1) {
+      g = t / wa;
+      r = t - g * wa;
+    } else {
+      const uint32_t t2 = (blockIdx.x - b1) * blockDim.x + threadIdx.x, rest = p.W - wa;
+      const uint32_t u = t2 / rest;
+      if (u >= mw.split_cnt[1]) return;
+      g = mw.uns_list[u];
+      r = wa + (t2 - u * rest);
+    }
+    t = g * per_group + r;  // the output's address stays g W + w
+  } else {
+    g = t / per_group;
+    r = t - g * per_group;
+  }
   if (g >= p.groups || (g << p.m_log2) >= entry_count(count_ptr, n)) return;
-  const uint32_t r = t - g * per_group, wdx = r / p.P, part = r % p.P;
+  const uint32_t wdx = r / p.P, part = r % p.P;
+  const uint32_t top = gsplit && gsplit[g] ? wa - 1 : p.W - 1;  // Horner's start
   const uint32_t s = p.H / p.P;
   ge_p3 U, T;
   bool u_set = false, t_set = false;
@@ -916,7 +1171,7 @@ k_msm_wpart(const uint32_t *count_ptr, uint32_t n, MsmWork mw, MsmParams p) {
     mw.wpart[2ull * t] = T;
     mw.wpart[2ull * t + 1] = U;
   } else {  // T is the window sum: k_msm_horner reads it
-    store_window_sum(&mw.wpart[2ull * t], T, wdx == p.W - 1);
+    store_window_sum(&mw.wpart[2ull * t], T, wdx == top);
   }
 }
 
@@ -952,7 +1207,8 @@ k_msm_wsum(const uint32_t *count_ptr, uint32_t n, MsmWork mw, MsmParams p) {
 template <bool SR, bool KM, bool LOC>
 __device__ __forceinline__ void horner_block(uint32_t bx, const uint32_t *count_ptr, uint32_t n, MsmWork mw,
                                              const MsmParams &p, const uint32_t *__restrict__ group_run0,
-                                             uint32_t n_runs) {
+                                             uint32_t n_runs, const uint8_t *__restrict__ gsplit = nullptr,
+                                             uint32_t wa = 0) {
   const uint32_t live_groups = (entry_count(count_ptr, n) + p.m() - 1) >> p.m_log2;
   if (bx * 16 >= live_groups) return;  // block-uniform
   const uint32_t raw = bx * 16 + (threadIdx.x >> 2);
@@ -963,9 +1219,12 @@ __device__ __forceinline__ void horner_block(uint32_t bx, const uint32_t *count_
   // in place (k_msm_wsum does not run)
   const uint32_t st = p.P == 1 ? 2 : 1;
   const ge_p3 *S = p.P == 1 ? mw.wpart + 2ull * g * p.W : mw.wsum + (size_t)g * p.W;
-  fe acc = reinterpret_cast<const fe *>(&S[st * (p.W - 1)])[c];
+  // a split group (split.h) starts at its own top window: quads are
+  // group-uniform, so whole quads stay active
+  const uint32_t top = gsplit && gsplit[g] ? wa - 1 : p.W - 1;
+  fe acc = reinterpret_cast<const fe *>(&S[st * top])[c];
   fe r, q, qc;
-  for (int wI = (int)p.W - 2; wI >= 0; wI--) {
+  for (int wI = (int)top - 1; wI >= 0; wI--) {
     qc = reinterpret_cast<const fe *>(&S[st * wI])[c];  // CachedQ (store_window_sum), loaded ahead
     for (uint32_t d = 0; d < p.c; d++) {
       quad::dbl(r, acc);
@@ -1011,8 +1270,8 @@ __device__ __forceinline__ void horner_block(uint32_t bx, const uint32_t *count_
 template <bool SR, bool KM, bool LOC = false>
 __global__ void __launch_bounds__(64)
 k_msm_horner(const uint32_t *count_ptr, uint32_t n, MsmWork mw, MsmParams p, const uint32_t *__restrict__ group_run0,
-             uint32_t n_runs) {
-  horner_block<SR, KM, LOC>(blockIdx.x, count_ptr, n, mw, p, group_run0, n_runs);
+             uint32_t n_runs, const uint8_t *__restrict__ gsplit, uint32_t wa) {
+  horner_block<SR, KM, LOC>(blockIdx.x, count_ptr, n, mw, p, group_run0, n_runs, gsplit, wa);
 }
 
 // Horner with helpers (launches below the located fallback's size): blocks
@@ -1325,20 +1584,17 @@ k_msm_subcheck(const uint8_t *__restrict__ sig, const uint32_t *__restrict__ idx
   if (live && c == 0) mw.sub_ok[e0 >> kSubGroupLog2] = ok ? 1 : 0;
 }
 
-// Dynamic LDS of k_msm_sort: the bucket counters / cursors, the scalar
-// reduction, the scan, and one window's staged entries (point, bucket).
-// (the run merge's tables alias everything behind the histogram: 3 x 2m
-// table words, a counter, 16 limbs per run)
-static size_t sort_smem(const MsmParams &p, uint32_t bs) {
-  const size_t sort = bs * 9 + bs + 1 + 2 * (2 * p.m() + 1);
-  const size_t merge = 6 * p.m() + 1 + 16 * merge_runs(p);
-  return ((size_t)p.W * p.H + std::max(sort, merge)) * sizeof(uint32_t);
+// Dynamic LDS of k_msm_sort (sort_words).
+static size_t sort_smem(const MsmParams &p, uint32_t bs, bool split = false) {
+  return ((size_t)sort_words(p, bs) + (split ? kSplitWords : 0)) * sizeof(uint32_t);
 }
 
 #ifdef TMV_CHECKS
 // Test build: every bucket with entries must have a sum written by this
 // launch.  The bucket sums are zeroed before the accumulation runs, so a
-// bucket whose join was lost keeps Z == 0 and is counted here.
+// bucket whose join was lost keeps Z == 0 and is counted here.  (A split
+// group, split.h, uses the buckets of its low windows only; k_msm_sort writes
+// a count of 0 for the rest, so they are passed over like any empty bucket.)
 __global__ void __launch_bounds__(256)
 k_check_buckets(const uint32_t *count_ptr, uint32_t n, MsmWork mw, MsmParams p) {
   const uint32_t live_groups = (entry_count(count_ptr, n) + p.m() - 1) >> p.m_log2;
@@ -1358,6 +1614,11 @@ k_check_buckets(const uint32_t *count_ptr, uint32_t n, MsmWork mw, MsmParams p) 
 // at least this many groups: kMsmCompactGroups, or the test aid's value
 // (tmv_internal_option "compact_groups"; 0 restores the default), so that
 // tests reach the compact order at small shapes.
+// Split key scalars (split.h): the launch's parameters ask for them
+// (tmverify_runtime.cpp msm_params), its sort merges runs, and its workspace
+// holds the lists.
+static bool split_on(const MsmWork &mw, const MsmParams &p) { return p.split && mw.merge_pk && mw.grp_split; }
+
 static std::atomic<uint32_t> g_compact_groups{kMsmCompactGroups};
 void set_compact_groups(uint32_t g) { g_compact_groups = g ? g : kMsmCompactGroups; }
 static bool compact_on(const MsmParams &p) { return p.groups >= g_compact_groups.load(std::memory_order_relaxed); }
@@ -1365,8 +1626,10 @@ static bool compact_on(const MsmParams &p) { return p.groups >= g_compact_groups
 // Bucket sums, window parts and window sums (shared by both forms).
 // timed: bracket the first two kernels with the live kernel timer (the
 // located fallback's second pass over the failing groups is not timed).
+// loc: the located pass over the failing groups' slots (a split launch's
+// groups then use p.Wl windows, and the second half of mw.grp_split).
 static hipError_t launch_buckets(const uint32_t *count_ptr, uint32_t n, MsmWork mw, const MsmParams &p,
-                                 hipStream_t stream, bool timed = true) {
+                                 hipStream_t stream, bool timed = true, bool loc = false) {
   const uint64_t chunks = (uint64_t)p.groups * p.chunks_per_group();
   const uint32_t ablocks = (uint32_t)((chunks + 255) / 256), per_xcd = (ablocks + 7) / 8;
   hipError_t e;
@@ -1398,7 +1661,15 @@ static hipError_t launch_buckets(const uint32_t *count_ptr, uint32_t n, MsmWork 
 #endif
   const uint64_t parts = (uint64_t)p.groups * p.W * p.P;
   tk = timed ? ktimer::begin(ktimer::kWpart, stream) : nullptr;
-  hipLaunchKernelGGL(k_msm_wpart, dim3((uint32_t)((parts + 255) / 256)), dim3(256), 0, stream, count_ptr, n, mw, p);
+  if (split_on(mw, p)) {  // two lane ranges: windows [0, wa) of every group, the rest of the unsplit groups
+    const uint32_t wa = loc ? p.Wl : p.Wa;
+    const uint64_t b1 = ((uint64_t)p.groups * wa + 255) / 256, b2 = ((uint64_t)p.groups * (p.W - wa) + 255) / 256;
+    hipLaunchKernelGGL(k_msm_wpart, dim3((uint32_t)(b1 + b2)), dim3(256), 0, stream, count_ptr, n, mw, p,
+                       (const uint8_t *)mw.grp_split + (loc ? p.groups : 0), wa);
+  } else {
+    hipLaunchKernelGGL(k_msm_wpart, dim3((uint32_t)((parts + 255) / 256)), dim3(256), 0, stream, count_ptr, n, mw, p,
+                       (const uint8_t *)nullptr, 0u);
+  }
   if ((e = hipGetLastError()) != hipSuccess) return e;
   ktimer::end(tk, stream);
   if (p.P == 1) return hipSuccess;  // the parts are the window sums
@@ -1510,6 +1781,14 @@ static MsmWork msm_view(MsmWork mw, const MsmParams &p, uint32_t n, uint64_t g0)
   mw.wsum += g0 * p.W;
   mw.group_ok += g0;
   mw.sort_ovf += g0;  // [g] of the part's groups (the located half is the tail's, full structs)
+  if (mw.grp_split) {  // likewise; the lists and their counters are the view's own
+    mw.grp_split += g0;
+    mw.hi_of += e0;
+    mw.hi_list += 2 * g0 * p.split_max;
+    mw.uns_list += g0;
+    mw.split_cnt += 2 * g0;
+    mw.g_base = (uint32_t)g0;
+  }
   if (mw.sub_ok) mw.sub_ok += (g0 << p.m_log2) / kSubGroup;
   if (mw.tabR) mw.tabR += 32 * e0;
   return mw;
@@ -1525,6 +1804,22 @@ static hipError_t launch_sort(const uint8_t *sig, const uint32_t *idx, const uin
                               uint32_t e_base, const fe *btab_q, Ed25519Work w, MsmWork mw, const MsmParams &p,
                               const MsmSeed &seed, uint8_t *out, int aligned, hipStream_t stream) {
   mw.compact = compact_on(p) ? 1 : 0;  // launch_buckets decides the same way
+  if constexpr (!SR) {
+    if (split_on(mw, p)) {
+      // the view's list counters (high points, unsplit groups): this sort appends to both
+      hipError_t e = hipMemsetAsync(mw.split_cnt, 0, 2 * sizeof(uint32_t), stream);
+      if (e != hipSuccess) return e;
+      if (p.m_log2 <= 8)
+        hipLaunchKernelGGL((k_msm_sort<false, false, 64, LOC, true>), dim3(p.groups), dim3(64), sort_smem(p, 64, true),
+                           stream, sig, idx, count_ptr, n, w, mw, p, seed, btab_q, aligned, nullptr, nullptr, out,
+                           e_base);
+      else
+        hipLaunchKernelGGL((k_msm_sort<false, false, kMsmSortBlock, LOC, true>), dim3(p.groups), dim3(kMsmSortBlock),
+                           sort_smem(p, kMsmSortBlock, true), stream, sig, idx, count_ptr, n, w, mw, p, seed, btab_q,
+                           aligned, nullptr, nullptr, out, e_base);
+      return hipGetLastError();
+    }
+  }
   if (p.m_log2 <= 8)
     hipLaunchKernelGGL((k_msm_sort<SR, false, 64, LOC>), dim3(p.groups), dim3(64), sort_smem(p, 64), stream, sig, idx,
                        count_ptr, n, w, mw, p, seed, btab_q, aligned, nullptr, nullptr, out, e_base);
@@ -1550,6 +1845,11 @@ static hipError_t launch_part(const uint8_t *pk, const uint8_t *sig, const uint8
   if ((e = launch_sort<SR, false>(sig, idx, count_ptr, n, e_base, btab_q, w, mw, p, seed, out, aligned, stream)) !=
       hipSuccess)
     return e;
+  if (split_on(mw, p)) {  // the listed leaders' high points, before the bucket sums load them
+    const uint64_t hb = ((uint64_t)p.groups * p.split_max + kHiBlock / 4 - 1) / (kHiBlock / 4);
+    hipLaunchKernelGGL(k_msm_hi_points, dim3((uint32_t)hb), dim3(kHiBlock), 0, stream, w, mw, p);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
   return launch_buckets(count_ptr, n, mw, p, stream);
 }
 
@@ -1564,7 +1864,9 @@ static hipError_t launch_tail_stages(const uint8_t *sig, const uint32_t *idx, co
                                      const MsmSeed &seed, uint8_t *out, int aligned, hipStream_t stream) {
   hipError_t e;
   const bool located = locate_enabled(n, p);
-  const bool helped = !located && w.hs_buf;
+  const bool split = split_on(mw, p);
+  const uint8_t *gsplit = split ? mw.grp_split : nullptr;
+  const bool helped = !located && w.hs_buf && !split;  // (the split is for launches well above the helped size)
   const uint32_t hblocks = (p.groups + 15) / 16;
   if (helped) {
     hipLaunchKernelGGL(k_msm_horner_helped<SR>, dim3(hblocks + (n + 63) / 64), dim3(64), 0, stream, count_ptr, n, mw,
@@ -1572,7 +1874,7 @@ static hipError_t launch_tail_stages(const uint8_t *sig, const uint32_t *idx, co
     w.hs = w.hs_buf;  // the fallback below takes the reductions
   } else {
     hipLaunchKernelGGL((k_msm_horner<SR, false>), dim3(hblocks), dim3(64), 0, stream, count_ptr, n, mw, p, nullptr,
-                       0u);
+                       0u, gsplit, p.Wa);
   }
   if ((e = hipGetLastError()) != hipSuccess) return e;
   if (located) {
@@ -1582,9 +1884,9 @@ static hipError_t launch_tail_stages(const uint8_t *sig, const uint32_t *idx, co
         hipSuccess)
       return e;
     const uint32_t n_slots = p.groups << p.m_log2;
-    if ((e = launch_buckets(mw.loc_count, n_slots, mw, p, stream, false)) != hipSuccess) return e;
+    if ((e = launch_buckets(mw.loc_count, n_slots, mw, p, stream, false, true)) != hipSuccess) return e;
     hipLaunchKernelGGL((k_msm_horner<SR, false, true>), dim3((p.groups + 15) / 16), dim3(64), 0, stream,
-                       mw.loc_count, n_slots, mw, p, nullptr, 0u);
+                       mw.loc_count, n_slots, mw, p, nullptr, 0u, split ? mw.grp_split + p.groups : nullptr, p.Wl);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     hipLaunchKernelGGL(k_loc_search<SR>, dim3(p.groups), dim3(64), 0, stream, count_ptr, n, mw, p);
     if ((e = hipGetLastError()) != hipSuccess) return e;
@@ -1794,7 +2096,7 @@ static hipError_t launch_km(const uint8_t *pk, const uint8_t *sig, const uint8_t
   hipLaunchKernelGGL(k_msm_items, dim3((n_items + 15) / 16), dim3(kQuadBlock), 0, stream, runs, n_items, mw, kt, bcomb);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   hipLaunchKernelGGL((k_msm_horner<SR, true>), dim3((p.groups + 15) / 16), dim3(64), 0, stream, nullptr, n, mw, p,
-                     runs.group_run0, runs.n_runs);
+                     runs.group_run0, runs.n_runs, (const uint8_t *)nullptr, 0u);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   return launch_comb_fallback<SR>(sig, key_slot, runs.order, n, w, kt, bcomb, out, aligned, mw.group_ok, p.m_log2,
                                   stream);

@@ -550,11 +550,32 @@ int faulted_rc(Device &d) {
 // groups of 128; c = 5 measured faster (2.56M launch alone 20.95 -> 19.94 ms,
 // profiles/r05/ab_window.txt): fuller buckets (16 entries, one chunk) split
 // and join less, and the 2H-addition running-sum chain halves.  3.0 keeps
-// c = 5 for groups of 64 and 128.
+// c = 5 for groups of 64 and 128.  With split key scalars (split.h) a merged
+// group runs half the windows' running sums, so they weigh less than this
+// model says; the sweep on that build still has groups of 128 with c = 5
+// first (10.61 ms per step; c = 4 11.08, c = 6 11.13, groups of 64 11.37-12.32,
+// profiles/scalar_split/sweep.txt), so the weight stays.
 constexpr double kRunningSumWeight = 3.0;
 static double running_sum_weight() {  // A/B of the weight (TMV_RS_WEIGHT, read per launch)
   const char *e = tmv::ab_knob("TMV_RS_WEIGHT");
   return e ? atof(e) : kRunningSumWeight;
+}
+// Split key scalars (split.h): ed25519 launches of at least this many groups
+// whose running sums take one lane per window (P == 1, the throughput-bound
+// launches); smaller ones keep the long form, where the high-point chain
+// would sit in front of a latency-bound pipeline.  Test aid
+// (tmv_internal_option "split_groups", 0 restores the default): 1 forces the
+// split on at any size, and such a launch takes P = 1.
+static std::atomic<uint32_t> g_split_groups{tmv::kMsmSplitGroups};
+// Most leaders a group may have and still split (A/B knob TMV_SPLIT_MAX, 0 =
+// never split; test aid tmv_internal_option "split_max", 0 restores the default).  A high point costs ~1.0k field multiplications (c Ws
+// doublings and an inversion); a split group saves (W - Ws) H running-sum
+// steps of 17 and about as many doublings on Horner's chain, ~7.8k at c = 5:
+// break-even near 7-8 leaders.
+static std::atomic<uint32_t> g_split_max{tmv::kMsmSplitMax};
+static uint32_t split_max() {
+  const char *e = tmv::ab_knob("TMV_SPLIT_MAX");
+  return e ? (uint32_t)strtoul(e, nullptr, 10) : g_split_max.load(std::memory_order_relaxed);
 }
 tmv::MsmParams msm_params(uint32_t n, uint32_t m_log2, uint32_t c, bool merged = false, bool ed_only = false,
                           int sub = -1) {
@@ -584,6 +605,16 @@ tmv::MsmParams msm_params(uint32_t n, uint32_t m_log2, uint32_t c, bool merged =
   // sub-group bisection: the context's choice, else the default policy
   // (the key-merged form's fallback is the key-cached comb: never)
   p.sub = merged ? 0 : (sub < 0 ? (tmv::subcheck_enabled(m_log2) ? 1 : 0) : (uint32_t)sub);
+  // split key scalars: uncached ed25519 launches (the sort splits only where
+  // it merges runs), while every point index still fits the entries' word
+  const uint32_t sg = g_split_groups.load(std::memory_order_relaxed);
+  const uint32_t smax = tmv::split_max_for(p.m(), split_max());
+  if (!merged && ed_only && smax && (sg == 1 || (p.P == 1 && p.groups >= sg)) &&
+      2ull * n + 2 + (uint64_t)p.groups * smax < (1ull << 31)) {
+    p.split = 1;
+    p.split_max = smax;
+    p.P = 1;
+  }
   return p;
 }
 
@@ -842,7 +873,26 @@ static int init_device(Device &d) {
   // quad B tables: entry m = (m+1)B, then entry kBaseQuadEntries + m =
   // (m+1)[2^128]B (the half-size scalars' top digits), m < kBaseQuadEntries,
   // as (ymx, ypx, xy2d, 1)
-  std::vector<tmv::fe> bq(2 * 4 * tmv::kBaseQuadEntries);
+  // then, for window sizes c = 4..9, [2^(c Ws)]B: the B term's high point of
+  // split groups (split.h; k_msm_sort stores it beside B)
+  std::vector<tmv::fe> bq(2 * 4 * tmv::kBaseQuadEntries + 4 * 6);
+  for (uint32_t c = 4; c <= 9; c++) {
+    tmv::ge_p3 B;
+    tmv::ed25519_base_point(B);
+    const uint32_t sh = c * tmv::split_windows((254 + c - 1) / c);
+    for (uint32_t d = 0; d < sh; d++) {
+      tmv::ge_p1p1 t;
+      tmv::ge_p3_dbl(t, B);
+      tmv::ge_p1p1_to_p3(B, t);
+    }
+    tmv::ge_precomp pc;
+    tmv::ge_p3_to_precomp(pc, B);
+    tmv::fe *o = &bq[4 * (2 * tmv::kBaseQuadEntries + (c - 4))];
+    o[0] = pc.ymx;
+    o[1] = pc.ypx;
+    o[2] = pc.xy2d;
+    tmv::fe_one(o[3]);
+  }
   {
     tmv::ge_p3 B;
     tmv::ed25519_base_point(B);
@@ -936,15 +986,15 @@ static int init_device(Device &d) {
 }
 
 // The device's counters of stats launches (MsmWork::ent_total: bucket entries,
-// failing groups, located groups, entries left one by one; null if it could not be allocated: the
+// failing groups, located groups, entries left one by one, split groups, high points; null if it could not be allocated: the
 // launch then counts nothing).  Caller holds d.mu.
 static unsigned long long *entry_counter(Device &d) {
   if (!d.ent_tried) {
     d.ent_tried = true;
     void *p = nullptr;
-    if (hipMalloc(&p, 32) != hipSuccess) {
+    if (hipMalloc(&p, 64) != hipSuccess) {
       (void)hipGetLastError();
-    } else if (hipMemset(p, 0, 32) != hipSuccess) {  // (not on the caller's stream: the launch path stays asynchronous)
+    } else if (hipMemset(p, 0, 64) != hipSuccess) {  // (not on the caller's stream: the launch path stays asynchronous)
       (void)hipGetLastError();
       (void)hipFree(p);
     } else {
@@ -1599,6 +1649,16 @@ int tmv_internal_option(const char *name, int64_t value) {
   }
   if (name && !strcmp(name, "key_merge")) {
     tmv::set_key_merge(value != 0);
+    return 0;
+  }
+  // "split_groups": group count from which merged key scalars are split
+  // (split.h; 1 = every launch, 0 restores the default)
+  if (name && !strcmp(name, "split_groups")) {
+    g_split_groups = value <= 0 ? tmv::kMsmSplitGroups : (uint32_t)value;
+    return 0;
+  }
+  if (name && !strcmp(name, "split_max")) {
+    g_split_max = value <= 0 ? tmv::kMsmSplitMax : (uint32_t)value;
     return 0;
   }
   set_error("unknown internal option");
@@ -2475,6 +2535,24 @@ int tmv_bucket_entry_stats(tmv_ctx *ctx, uint64_t *entries) {
     t += v;
   }
   if (entries) *entries = t;
+  return 0;
+}
+
+int tmv_split_stats(tmv_ctx *ctx, uint64_t *groups_split, uint64_t *high_points) {
+  if (!ctx) return TMV_ERR_ARG;
+  uint64_t t[2] = {0, 0};
+  for (auto &d : ctx->devs) {
+    std::lock_guard<std::mutex> lk(d->mu);
+    if (!d->ent_total) continue;
+    unsigned long long v[6] = {0, 0, 0, 0, 0, 0};
+    hipError_t e = hipSetDevice(d->id);
+    if (e == hipSuccess) e = hipMemcpy(v, d->ent_total, sizeof(v), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) { set_error("split counters", e); return TMV_ERR_NO_DEVICE; }
+    t[0] += v[4];
+    t[1] += v[5];
+  }
+  if (groups_split) *groups_split = t[0];
+  if (high_points) *high_points = t[1];
   return 0;
 }
 
