@@ -42,7 +42,7 @@ extern "C" {
  * forever).  The context's device work is then in an unknown state: the
  * context refuses further work (every call returns TMV_ERR_TIMEOUT); the
  * caller verifies on the CPU and may tmv_close / tmv_open a new context.
- * Pages of the caller's buffers (inputs and status array) that a streamed
+ * Pages of the caller's input buffers (pk, sig, msg, kind) that a streamed
  * call had registered for direct DMA stay page-locked after a failed call: the
  * device may still read them, so they are never unregistered under it (and
  * the library keeps no record that could unregister them once reused). */

@@ -1,5 +1,5 @@
 // Part boundaries and caller-page locking of a streamed host-buffer chunk
-// (tmverify_runtime.cpp, stage_and_launch / batch_check /
+// (tmverify_runtime.cpp, stage_streamed / batch_check /
 // mixed_check_streamed).  Pure host arithmetic, unit-tested on the CPU
 // (tests/test_stream_plan.py through tests/native/commit_check.cpp).
 #pragma once

@@ -35,10 +35,10 @@ struct StagedCall {
   int open() {
     lk = std::unique_lock<std::mutex>(d->mu);
     if (d->faulted) return faulted_rc(*d);
-    hipError_t e = hipSetDevice(d->id);
-    if (e != hipSuccess) { set_error("hipSetDevice", e); return TMV_ERR_NO_DEVICE; }
-    if (!(s = context_stream(*d))) { set_error("hipStreamCreate failed"); return TMV_ERR_NO_DEVICE; }
-    return (e = wait_stream(*d, s)) != hipSuccess ? wait_rc(e) : 0;
+    const int rc = use_device(*d, nullptr, &s);
+    if (rc != 0) return rc;
+    const hipError_t e = wait_stream(*d, s);
+    return e != hipSuccess ? wait_rc(e) : 0;
   }
   int reserve(const tmh::StageLayout &layout, DeviceBuf &hb, DeviceBuf &db, bool via_pinned) {
     L = &layout;

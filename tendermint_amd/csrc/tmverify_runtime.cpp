@@ -32,6 +32,7 @@
 #include "ed25519_core.h"
 #include "merlin_dev.h"
 #include "host/pool.h"
+#include "host/key_order.h"
 #include "host/shard_plan.h"
 #include "host/stream_plan.h"
 #include "host/shard_run.h"
@@ -217,6 +218,16 @@ struct HostLane {
   void unpin() {
     for (void *p : pinned) (void)hipHostUnregister(p);
     pinned.clear();
+  }
+  // The staging of a chunk of n entries with in_bytes of inputs, pinned and
+  // on the device; 0 or TMV_ERR_NOMEM.
+  int reserve(size_t in_bytes, uint32_t n) {
+    hipError_t e;
+    if ((e = h_in.ensure(in_bytes, true)) != hipSuccess) { set_error("hipHostMalloc", e); return TMV_ERR_NOMEM; }
+    if ((e = d_in.ensure(in_bytes, false)) != hipSuccess) { set_error("hipMalloc", e); return TMV_ERR_NOMEM; }
+    if ((e = h_out.ensure(n, true)) != hipSuccess) { set_error("hipHostMalloc", e); return TMV_ERR_NOMEM; }
+    if ((e = d_out.ensure(n, false)) != hipSuccess) { set_error("hipMalloc", e); return TMV_ERR_NOMEM; }
+    return 0;
   }
 };
 constexpr int kLanes = 4;  // streams per device; TMV_HOST_LANES of them carry chunks
@@ -535,6 +546,16 @@ int wait_rc(hipError_t e) { return e == hipErrorNotReady ? TMV_ERR_TIMEOUT : TMV
 int faulted_rc(Device &d) {
   set_error("device timed out earlier (TMV_ERR_TIMEOUT); open a new context");
   return TMV_ERR_TIMEOUT;
+}
+// Makes d the current device and, where s is given, picks the stream of a call
+// on it: the caller's, else the context's own.  0 or TMV_ERR_NO_DEVICE.
+int use_device(Device &d, void *stream = nullptr, hipStream_t *s = nullptr) {
+  const hipError_t e = hipSetDevice(d.id);
+  if (e != hipSuccess) { set_error("hipSetDevice", e); return TMV_ERR_NO_DEVICE; }
+  if (!s) return 0;
+  *s = stream ? static_cast<hipStream_t>(stream) : context_stream(d);
+  if (!*s) { set_error("hipStreamCreate failed"); return TMV_ERR_NO_DEVICE; }
+  return 0;
 }
 
 // Batch-equation parameters for n entries.  Group size: the caller's, else
@@ -1283,7 +1304,7 @@ static Workspace *reserve_work(Device &d, uint32_t n, bool mixed, hipStream_t s,
 }
 
 // Stages the inputs of entries [e0, e1) of a streamed launch and enqueues
-// their copy; *ready = an event recorded after it (stage_and_launch); 0 or < 0.
+// their copy; *ready = an event recorded after it (StreamFeeder); 0 or < 0.
 using PartFeeder = std::function<int(uint32_t e0, uint32_t e1, hipEvent_t *ready)>;
 
 // Part boundaries of a streamed launch of n entries: whole groups, the first
@@ -1821,22 +1842,315 @@ struct VoteSrc {
   const VoteExtSrc *ext = nullptr;  // extension entries after the votes (vote_ext_runtime.h)
 };
 
-// Stage one contiguous shard [lo, hi) to device d and launch; does not sync.
-// Layout: pk | sig | off | msg | kind or key slots | votes | templates | key
-// runs | key order (16-B aligned pieces).  Key-cached batches resolve their
-// slots first; the key-merged batch equation gets the key order of the
-// entries (a counting sort by slot) and the runs of one key inside a group,
-// and its kernels read the entries through that order.
-static int stage_and_launch(tmv_ctx *ctx, uint32_t flags, Device &d, HostLane &ln, Scheme sch, const uint8_t *kind,
-                            const uint8_t *pk, const uint8_t *sig, const uint8_t *msg, const uint32_t *msg_off,
-                            uint32_t lo, uint32_t hi, const VoteSrc *vs) {
+// One chunk [lo, lo + n) of a host-buffer call, on its device and lane, with
+// the packed front of its staging (Layout: pk | sig | off | msg).
+struct HostChunk {
+  tmv_ctx *ctx;
+  Device &d;
+  HostLane &ln;
+  const uint8_t *kind, *pk, *sig, *msg;
+  const uint32_t *msg_off;
+  uint32_t lo, n;
+  const VoteSrc *vs;
+  size_t mbytes;
+  Layout L;
+};
+
+// The chunk's statuses come back through the lane's staging (a late DMA after
+// a device timeout must not land in caller memory the call no longer owns);
+// run_batch hands them to the caller after its wait.
+static int statuses_to_lane(const HostChunk &c) {
+  const hipError_t e = hipMemcpyAsync(c.ln.h_out.ptr, c.ln.d_out.ptr, c.n, hipMemcpyDeviceToHost, c.ln.stream);
+  if (e != hipSuccess) { set_error("hipMemcpyAsync(D2H)", e); return TMV_ERR_LAUNCH; }
+  c.ctx->m_d2h += c.n;
+  return 0;
+}
+
+namespace {
+// The PartFeeder of a streamed chunk: stages entries [a, b) of the chunk and
+// enqueues their copy on the lane's copy stream, one call per part.
+struct StreamFeeder {
+  const HostChunk &c;
+  const bool mixed;  // mixed chunks: the kind bytes too, after the other inputs
+  const size_t kind_at = c.L.total;
+  uint8_t *const h = static_cast<uint8_t *>(c.ln.h_in.ptr), *const dd = static_cast<uint8_t *>(c.ln.d_in.ptr);
+  size_t part = 0;
+  double pin_ms = 0;
+  tmh::SpanPins reg[4] = {};  // host/stream_plan.h; the spans: pk, sig, msg, kind
+  // per span: [dst offset, caller bytes, length]; [d0, d1) of it is DMA'd
+  // from registered pages (split at cut), the rest staged: a head [0, d0) and
+  // a tail [d1, len), which is all of it (d0 = d1 = cut = 0) with no such pages
+  struct Span {
+    size_t at;
+    const uint8_t *src;
+    size_t len, d0, d1, cut;
+  };
+
+  int operator()(uint32_t a, uint32_t b, hipEvent_t *ready) {
+    uint32_t *off = reinterpret_cast<uint32_t *>(h + c.L.off);
+    const uint32_t lo = c.lo, base = c.msg_off[lo];
+    for (uint32_t i = a; i <= b; i++) off[i] = c.msg_off[lo + i] - base;
+    const size_t m0 = off[a], m1 = off[b];
+    Span sp[4] = {{c.L.pk + 32ull * a, c.pk + 32ull * (lo + a), 32ull * (b - a), 0, 0, 0},
+                  {c.L.sig + 64ull * a, c.sig + 64ull * (lo + a), 64ull * (b - a), 0, 0, 0},
+                  {c.L.msg + m0, c.msg + base + m0, m1 - m0, 0, 0, 0},
+                  {kind_at + a, mixed ? c.kind + lo + a : nullptr, mixed ? (size_t)(b - a) : 0, 0, 0, 0}};
+    if (g_register) pin(sp);
+    CopySpan cs[8];
+    size_t ncs = 0;
+    for (const Span &x : sp) {
+      if (x.d0) cs[ncs++] = {h + x.at, x.src, x.d0};
+      if (x.d1 < x.len) cs[ncs++] = {h + x.at + x.d1, x.src + x.d1, x.len - x.d1};
+    }
+    par_memcpy_spans(cs, ncs);
+    return enqueue(sp, a, b, ready);
+  }
+
+  // Caller pages pinned for direct DMA, per span (pk, sig, msg, kind): the
+  // whole pages inside part 0's bytes, then at part 1 every whole page
+  // inside the rest of the chunk's span, in one range (registering costs
+  // ~2 us a range and unregistering ~4.5 us: a 2.56M call used to unpin 63
+  // per-part ranges in 0.28 ms, and stage a sub-page tail per part and
+  // span).  Only pages wholly inside the caller's span are registered, so
+  // a neighbouring buffer's registration never collides; the bytes outside
+  // the registered pages (part 0's head and tail, the chunk's last tail)
+  // go through the lane's pinned staging, and so does a span whose range
+  // cannot be registered (read-only, already registered), for the rest of
+  // the chunk.
+  void pin(Span (&sp)[4]) {
+    constexpr uintptr_t kPage = 4096;
+    const uint32_t end = c.lo + c.n;
+    const uintptr_t span_end[4] = {(uintptr_t)(c.pk + 32ull * end), (uintptr_t)(c.sig + 64ull * end),
+                                   c.mbytes ? (uintptr_t)(c.msg + c.msg_off[end]) : 0,
+                                   mixed ? (uintptr_t)(c.kind + end) : 0};
+    const auto t0 = std::chrono::steady_clock::now();
+    for (int k = 0; k < 4; k++) {
+      Span &x = sp[k];
+      tmh::SpanPins &r = reg[k];
+      if (r.failed || x.len < 4 * kPage) continue;
+      const uintptr_t s0 = (uintptr_t)x.src, s1 = s0 + x.len;
+      uintptr_t r0, r1;
+      if (tmh::next_pin_range(r, s0, s1, span_end[k], kPage, &r0, &r1)) {
+        if (hipHostRegister(reinterpret_cast<void *>(r0), r1 - r0, hipHostRegisterDefault) != hipSuccess) {
+          (void)hipGetLastError();
+          r.failed = true;  // stage this span for the rest of the chunk
+          continue;
+        }
+        c.ln.pinned.push_back(reinterpret_cast<void *>(r0));
+        tmh::commit_pin_range(r, r0, r1);
+      }
+      tmh::direct_piece(r, s0, s1, &x.d0, &x.d1, &x.cut);
+    }
+    pin_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  }
+  bool h2d(size_t at, const void *src, size_t len) const {
+    if (!len) return true;
+    const hipError_t e = hipMemcpyAsync(dd + at, src, len, hipMemcpyHostToDevice, c.ln.copy);
+    if (e != hipSuccess) { set_error("hipMemcpyAsync(H2D)", e); return false; }
+    c.ctx->m_h2d += len;
+    return true;
+  }
+  // The part's copies on the copy stream, then its event.
+  int enqueue(const Span (&sp)[4], uint32_t a, uint32_t b, hipEvent_t *ready) {
+    HostLane &ln = c.ln;
+    hipError_t e;
+    if (part >= ln.part_ready.size()) {
+      hipEvent_t ev;
+      if ((e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) {
+        set_error("hipEventCreate", e);
+        return TMV_ERR_NO_DEVICE;
+      }
+      ln.part_ready.push_back(ev);
+    }
+    if (!h2d(c.L.off + 4ull * a, h + c.L.off + 4ull * a, 4ull * (b - a + 1))) return TMV_ERR_LAUNCH;
+    for (const Span &x : sp) {  // staged head, the locked middle (one DMA per locked range), staged tail
+      assert(x.d0 <= x.cut && x.cut <= x.d1 && x.d1 <= x.len);  // direct_piece; all 0 with no locked pages
+      if (!h2d(x.at, h + x.at, x.d0) || !h2d(x.at + x.d0, x.src + x.d0, x.cut - x.d0) ||
+          !h2d(x.at + x.cut, x.src + x.cut, x.d1 - x.cut) || !h2d(x.at + x.d1, h + x.at + x.d1, x.len - x.d1))
+        return TMV_ERR_LAUNCH;
+    }
+    *ready = ln.part_ready[part++];
+    if ((e = hipEventRecord(*ready, ln.copy)) != hipSuccess) { set_error("part event", e); return TMV_ERR_LAUNCH; }
+    return 0;
+  }
+};
+}  // namespace
+
+// Streamed chunk: staged and copied part by part, each part's kernels behind
+// its copy (mixed chunks: the kind bytes too, after the other inputs).
+static int stage_streamed(const HostChunk &c, const LaunchOpts &o, bool sr, bool mixed, EngineTimer &tm) {
+  HostLane &ln = c.ln;
+  const Layout &L = c.L;
+  int rc = ln.reserve(L.total + (mixed ? align16(c.n) : 0), c.n);
+  if (rc != 0) return rc;
+  hipError_t e;
+  if (!ln.copy && (e = hipStreamCreateWithFlags(&ln.copy, hipStreamNonBlocking)) != hipSuccess) {
+    ln.copy = nullptr;
+    set_error("hipStreamCreate", e);
+    return TMV_ERR_NO_DEVICE;
+  }
+  if ((g_stream_two || mixed) && !ln.helper) {
+    if (hipStreamCreateWithFlags(&ln.helper, hipStreamNonBlocking) != hipSuccess) ln.helper = nullptr;
+    else if (hipEventCreateWithFlags(&ln.join, hipEventDisableTiming) != hipSuccess) ln.join = nullptr;
+  }
+  ln.unpin();
+  StreamFeeder feeder{c, mixed};
+  const PartFeeder feed = std::ref(feeder);
+  tm.mark("stage", c.n);
+  const uint8_t *dd = feeder.dd;
+  const uint32_t *doff = reinterpret_cast<const uint32_t *>(dd + L.off);
+  uint8_t *out = static_cast<uint8_t *>(ln.d_out.ptr);
+  rc = mixed ? mixed_check_streamed(c.d, o, c.kind + c.lo, dd + feeder.kind_at, dd + L.pk, dd + L.sig, dd + L.msg, doff,
+                                    c.n, out, ln.stream, ln.helper, ln.join, ln.part_split, feed)
+             : batch_check(c.d, o, sr, dd + L.pk, dd + L.sig, dd + L.msg, doff, c.n, out, ln.stream, &feed,
+                           g_stream_two ? ln.helper : nullptr, g_stream_two ? ln.join : nullptr);
+  if (rc == 0) {
+    if (tm.on) fprintf(stderr, "[tmv_engine] pinning %9.3f ms (%zu ranges)\n", feeder.pin_ms, ln.pinned.size());
+    tm.mark("parts staged + launched", c.n);
+    rc = statuses_to_lane(c);
+  }
+  if (rc != 0) {
+    // an error after parts were enqueued: they still use the lane's buffers
+    // and the caller's registered pages, so drain before returning
+    const bool drained = wait_stream(c.d, ln.copy) == hipSuccess;
+    if (ln.helper) (void)wait_stream(c.d, ln.helper);
+    if (wait_stream(c.d, ln.stream) == hipSuccess && drained) ln.unpin();
+    else ln.pinned.clear();  // copies may be in flight: leave the pages registered (see run_batch)
+  }
+  return rc;
+}
+
+// Whole chunk: staged in one piece behind the packed front,
+//   kind or key slots | votes | templates | extension entries | key runs | key order
+// (16-B aligned pieces), copied in one piece and launched by scheme.  The
+// key-merged batch equation gets the key order of the entries and the runs of
+// one key inside a group (host/key_order.h, from the histogram launch_chunk
+// left in d.key_count), and its kernels read the entries through that order.
+static int stage_whole(const HostChunk &c, const LaunchOpts &o, Scheme sch, bool merged, uint32_t distinct,
+                       EngineTimer &tm) {
+  Device &d = c.d;
+  HostLane &ln = c.ln;
+  const Layout &L = c.L;
+  const VoteSrc *vs = c.vs;
+  const uint32_t n = c.n, lo = c.lo, hi = lo + n;
+  const bool cached = sch == Scheme::Ed25519Cached || sch == Scheme::Sr25519Cached;
+  const bool sr = sch == Scheme::Sr25519Cached || sch == Scheme::Sr25519;
+  const uint32_t G = merged ? o.p.groups : 0;
+  const tmh::KeyRunRegion R(distinct, G);
+  size_t total = L.total;
+  auto region = [&total](size_t bytes) {  // the next one, from a 16-byte boundary (none for 0 bytes)
+    const size_t at = total;
+    total += align16(bytes);
+    return at;
+  };
+  const VoteExtSrc *ext = vs ? vs->ext : nullptr;
+  const size_t kind_at = region(sch == Scheme::Mixed ? n : cached ? 4ull * n : 0);
+  const size_t votes_at = region(vs ? sizeof(tmv_vote) * vote_ext_plan(ext, lo, hi, 0).nv : 0);
+  const size_t tab_at = region(vs ? vs->tab_bytes : 0);
+  const VoteExtStage xe = vote_ext_plan(ext, lo, hi, total);  // vote / extension entries of the chunk
+  total = xe.end;
+  const size_t runs_at = region(merged ? R.bytes() : 0);
+  const size_t order_at = region(merged ? 4ull * n : 0);
+  int rc = ln.reserve(total, n);
+  if (rc != 0) return rc;
+  uint8_t *h = static_cast<uint8_t *>(ln.h_in.ptr);
+  uint32_t *off = reinterpret_cast<uint32_t *>(h + L.off);
+  const uint32_t base = c.msg_off[lo];
+  par_memcpy(h + L.pk, c.pk + 32ull * lo, 32ull * n);
+  par_memcpy(h + L.sig, c.sig + 64ull * lo, 64ull * n);
+  for (uint32_t i = 0; i <= n; i++) off[i] = c.msg_off[lo + i] - base;
+  if (vs) {
+    if (xe.nv) par_memcpy(h + votes_at, vs->votes + lo, sizeof(tmv_vote) * xe.nv);
+    std::memcpy(h + tab_at, vs->tab, vs->tab_bytes);
+    if (ext) vote_ext_stage(*ext, xe, h);
+  } else if (c.mbytes) {
+    par_memcpy(h + L.msg, c.msg + base, c.mbytes);
+  }
+  if (sch == Scheme::Mixed) std::memcpy(h + kind_at, c.kind + lo, n);
+  if (cached) std::memcpy(h + kind_at, d.slots.data(), 4ull * n);
+  uint32_t n_runs = 0;
+  if (merged) {
+    uint32_t *runs = reinterpret_cast<uint32_t *>(h + runs_at);
+    n_runs = tmh::key_order_runs(d.key_count.data(), d.slots.data(), n, d.kcap, o.p.m_log2, G,
+                                 reinterpret_cast<uint32_t *>(h + order_at), runs, runs + R.slot_at,
+                                 runs + R.group_run0_at);
+  }
+  tm.mark("stage", n);
+  // Small key-cached batches (the VerifyCommit latency path) skip both
+  // copies: the fused kernel reads the pinned staging and writes the
+  // statuses to pinned memory over PCIe (coherent host memory).
+  const bool zero_copy = g_zero_copy && cached && !merged && !vs && n <= g_cached_fused_max && ln.h_in.dev &&
+                         ln.h_out.dev;
+  uint8_t *dd = static_cast<uint8_t *>(zero_copy ? ln.h_in.dev : ln.d_in.ptr);
+  const uint32_t *doff = reinterpret_cast<uint32_t *>(dd + L.off);
+  hipError_t e;
+  if (zero_copy) {
+    // inputs are read in place
+  } else if (vs) {  // everything but the message region, which the device writes
+    if ((e = hipMemcpyAsync(dd, h, L.msg, hipMemcpyHostToDevice, ln.stream)) != hipSuccess ||
+        (e = hipMemcpyAsync(dd + L.total, h + L.total, total - L.total, hipMemcpyHostToDevice, ln.stream)) !=
+            hipSuccess) {
+      set_error("hipMemcpyAsync(H2D)", e);
+      return TMV_ERR_LAUNCH;
+    }
+    c.ctx->m_h2d += L.msg + (total - L.total);
+    const tmv::VoteTab *tab = reinterpret_cast<const tmv::VoteTab *>(dd + tab_at);
+    if ((e = tmv::launch_vote_signbytes(reinterpret_cast<const tmv_vote *>(dd + votes_at), tab,
+                                        dd + tab_at + vs->blob_at, doff, xe.nv, dd + L.msg, ln.stream)) != hipSuccess) {
+      set_error("k_vote_signbytes", e);
+      return TMV_ERR_LAUNCH;
+    }
+    if (ext && (e = vote_ext_launch(*ext, xe, dd, doff, dd + L.msg, ln.stream)) != hipSuccess) {
+      set_error("k_vote_ext_signbytes", e);
+      return TMV_ERR_LAUNCH;
+    }
+  } else if ((e = hipMemcpyAsync(ln.d_in.ptr, h, total, hipMemcpyHostToDevice, ln.stream)) != hipSuccess) {
+    set_error("hipMemcpyAsync(H2D)", e);
+    return TMV_ERR_LAUNCH;
+  } else {
+    c.ctx->m_h2d += total;
+  }
+  uint8_t *out = static_cast<uint8_t *>(zero_copy ? ln.h_out.dev : ln.d_out.ptr);
+  const uint32_t *dslots = reinterpret_cast<const uint32_t *>(dd + kind_at);
+  switch (sch) {
+    case Scheme::Ed25519:
+      rc = launch_ed25519(d, o, dd + L.pk, dd + L.sig, dd + L.msg, doff, n, out, ln.stream);
+      break;
+    case Scheme::Sr25519:
+      rc = launch_sr25519(d, o, dd + L.pk, dd + L.sig, dd + L.msg, doff, n, reinterpret_cast<int8_t *>(out), ln.stream);
+      break;
+    case Scheme::Ed25519Cached:
+    case Scheme::Sr25519Cached:
+      if (merged) {
+        const uint32_t *runs = reinterpret_cast<const uint32_t *>(dd + runs_at);
+        const tmv::KeyRuns kr{runs, runs + R.slot_at, runs + R.group_run0_at,
+                              reinterpret_cast<const uint32_t *>(dd + order_at), n_runs};
+        rc = launch_key_merged(d, o, sr, dd + L.pk, dd + L.sig, dd + L.msg, doff, dslots, kr, n, out, ln.stream);
+      } else {
+        rc = launch_cached(d, sr, dd + L.pk, dd + L.sig, dd + L.msg, doff, dslots, n, out, ln.stream);
+      }
+      break;
+    default:
+      rc = launch_mixed(d, o, dd + kind_at, dd + L.pk, dd + L.sig, dd + L.msg, doff, n, reinterpret_cast<int8_t *>(out),
+                        ln.stream);
+  }
+  if (rc != 0 || zero_copy) return rc;
+  return statuses_to_lane(c);
+}
+
+// One contiguous shard [lo, hi) of a host-buffer call to device d: decides how
+// it runs, then stages and launches it (stage_streamed or stage_whole); does
+// not sync.  Key-cached batches resolve their slots first, and take the
+// key-merged batch equation while it is worth it (host/key_order.h).
+static int launch_chunk(tmv_ctx *ctx, uint32_t flags, Device &d, HostLane &ln, Scheme sch, const uint8_t *kind,
+                        const uint8_t *pk, const uint8_t *sig, const uint8_t *msg, const uint32_t *msg_off,
+                        uint32_t lo, uint32_t hi, const VoteSrc *vs) {
   const uint32_t n = hi - lo;
   const size_t mbytes = (size_t)msg_off[hi] - msg_off[lo];
-  Layout L(n, mbytes);
+  const HostChunk c{ctx, d, ln, kind, pk, sig, msg, msg_off, lo, n, vs, mbytes, Layout(n, mbytes)};
   bool cached = sch == Scheme::Ed25519Cached || sch == Scheme::Sr25519Cached;
   const bool sr = sch == Scheme::Sr25519Cached || sch == Scheme::Sr25519;
-  hipError_t e = hipSetDevice(d.id);
-  if (e != hipSuccess) { set_error("hipSetDevice", e); return TMV_ERR_NO_DEVICE; }
+  if (const int rc = use_device(d)) return rc;
   EngineTimer tm;
   if (cached) {
     d.slots.resize(n);
@@ -1850,323 +2164,20 @@ static int stage_and_launch(tmv_ctx *ctx, uint32_t flags, Device &d, HostLane &l
   tm.mark("keys", n);
   LaunchOpts o = make_opts(ctx, flags, n, cached, sch == Scheme::Ed25519 || sch == Scheme::Ed25519Cached);
   if (o.err) return o.err;
-  // key-merged form: worth it while a group holds few keys (runs <= n / 2)
   bool merged = cached && o.batch_eq;
   uint32_t distinct = 0;
-  const uint32_t kc = d.kcap;
-  constexpr uint32_t kSortChunks = 16;
-  if (merged) {  // per-chunk key histograms (parallel), for a stable counting sort
-    d.key_count.assign((size_t)kSortChunks * kc, 0);
-    const uint32_t *sl = d.slots.data();
-    uint32_t *hist = d.key_count.data();
-    tmh::parallel_for_n(kSortChunks, kSortChunks, [&](size_t c) {
-      const uint32_t j0 = (uint32_t)((uint64_t)n * c / kSortChunks), j1 = (uint32_t)((uint64_t)n * (c + 1) / kSortChunks);
-      uint32_t *hc = hist + c * kc;
-      for (uint32_t j = j0; j < j1; j++) hc[sl[j]]++;
-    });
-    for (uint32_t k = 0; k < kc; k++) {
-      uint32_t t = 0;
-      for (uint32_t c = 0; c < kSortChunks; c++) t += hist[(size_t)c * kc + k];
-      distinct += t != 0;
-    }
-    if ((uint64_t)distinct + o.p.groups > n / 2) merged = false;
+  if (merged) {  // the staging is sized by the distinct keys, so they are counted before it exists
+    d.key_count.resize((size_t)tmh::kKeySortChunks * d.kcap);
+    distinct = tmh::key_histogram(d.slots.data(), n, d.kcap, d.key_count.data());
+    merged = tmh::key_merge_worth(distinct, o.p.groups, n);
   }
   if (cached && !merged) o.batch_eq = false;  // key-cached per-entry path
   read_env();
   const bool mixed_stream = sch == Scheme::Mixed && g_mixed_stream;
   if (g_stream && !cached && !vs && (sch == Scheme::Ed25519 || sch == Scheme::Sr25519 || mixed_stream) &&
-      o.batch_eq && n > g_stream_first) {
-    // streamed: stage and copy part by part, each part's kernels behind its
-    // copy (mixed chunks: the kind bytes too, after the other inputs)
-    const size_t kind_at = L.total, in_total = L.total + (mixed_stream ? align16(n) : 0);
-    if ((e = ln.h_in.ensure(in_total, true)) != hipSuccess) { set_error("hipHostMalloc", e); return TMV_ERR_NOMEM; }
-    if ((e = ln.d_in.ensure(in_total, false)) != hipSuccess) { set_error("hipMalloc", e); return TMV_ERR_NOMEM; }
-    if ((e = ln.h_out.ensure(n, true)) != hipSuccess) { set_error("hipHostMalloc", e); return TMV_ERR_NOMEM; }
-    if ((e = ln.d_out.ensure(n, false)) != hipSuccess) { set_error("hipMalloc", e); return TMV_ERR_NOMEM; }
-    if (!ln.copy && (e = hipStreamCreateWithFlags(&ln.copy, hipStreamNonBlocking)) != hipSuccess) {
-      ln.copy = nullptr;
-      set_error("hipStreamCreate", e);
-      return TMV_ERR_NO_DEVICE;
-    }
-    uint8_t *h = static_cast<uint8_t *>(ln.h_in.ptr), *dd = static_cast<uint8_t *>(ln.d_in.ptr);
-    uint32_t *off = reinterpret_cast<uint32_t *>(h + L.off);
-    const uint32_t base = msg_off[lo];
-    size_t part = 0;
-    if ((g_stream_two || mixed_stream) && !ln.helper) {
-      if (hipStreamCreateWithFlags(&ln.helper, hipStreamNonBlocking) != hipSuccess) ln.helper = nullptr;
-      else if (hipEventCreateWithFlags(&ln.join, hipEventDisableTiming) != hipSuccess) ln.join = nullptr;
-    }
-    bool pin_ok = g_register != 0;
-    double pin_ms = 0;
-    ln.unpin();
-    // Caller pages pinned for direct DMA, per span (pk, sig, msg, kind): the
-    // whole pages inside part 0's bytes, then at part 1 every whole page
-    // inside the rest of the chunk's span, in one range (registering costs
-    // ~2 us a range and unregistering ~4.5 us: a 2.56M call used to unpin 63
-    // per-part ranges in 0.28 ms, and stage a sub-page tail per part and
-    // span).  Only pages wholly inside the caller's span are registered, so
-    // a neighbouring buffer's registration never collides; the bytes outside
-    // the registered pages (part 0's head and tail, the chunk's last tail)
-    // go through the lane's pinned staging, and so does a span whose range
-    // cannot be registered (read-only, already registered), for the rest of
-    // the chunk.
-    constexpr uintptr_t kPage = 4096;
-    tmh::SpanPins reg[4];  // host/stream_plan.h
-    const uintptr_t span_end[4] = {(uintptr_t)(pk + 32ull * (lo + n)), (uintptr_t)(sig + 64ull * (lo + n)),
-                                   mbytes ? (uintptr_t)(msg + msg_off[lo + n]) : 0,
-                                   mixed_stream ? (uintptr_t)(kind + lo + n) : 0};
-    const PartFeeder feed = [&](uint32_t a, uint32_t b, hipEvent_t *ready) -> int {
-      for (uint32_t i = a; i <= b; i++) off[i] = msg_off[lo + i] - base;
-      const size_t m0 = off[a], m1 = off[b];
-      // per span: [dst offset, caller bytes, length]; [d0, d1) of it is
-      // DMA'd from registered pages, the rest staged
-      struct Span {
-        size_t at;
-        const uint8_t *src;
-        size_t len;
-        size_t d0, d1, cut;
-      } sp[4] = {{L.pk + 32ull * a, pk + 32ull * (lo + a), 32ull * (b - a), 0, 0, 0},
-                 {L.sig + 64ull * a, sig + 64ull * (lo + a), 64ull * (b - a), 0, 0, 0},
-                 {L.msg + m0, msg + base + m0, m1 - m0, 0, 0, 0},
-                 {kind_at + a, mixed_stream ? kind + lo + a : nullptr, mixed_stream ? (size_t)(b - a) : 0, 0, 0, 0}};
-      const auto t0 = std::chrono::steady_clock::now();
-      for (int k = 0; k < 4; k++) {
-        Span &x = sp[k];
-        tmh::SpanPins &r = reg[k];
-        if (!pin_ok || r.failed || x.len < 4 * kPage) continue;
-        const uintptr_t s0 = (uintptr_t)x.src, s1 = s0 + x.len;
-        uintptr_t r0, r1;
-        if (tmh::next_pin_range(r, s0, s1, span_end[k], kPage, &r0, &r1)) {
-          if (hipHostRegister(reinterpret_cast<void *>(r0), r1 - r0, hipHostRegisterDefault) != hipSuccess) {
-            (void)hipGetLastError();
-            r.failed = true;  // stage this span for the rest of the chunk
-            continue;
-          }
-          ln.pinned.push_back(reinterpret_cast<void *>(r0));
-          tmh::commit_pin_range(r, r0, r1);
-        }
-        tmh::direct_piece(r, s0, s1, &x.d0, &x.d1, &x.cut);
-      }
-      pin_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-      CopySpan cs[8];
-      size_t ncs = 0;
-      for (const Span &x : sp) {
-        if (!x.len) continue;
-        if (x.d1 == 0) {
-          cs[ncs++] = {h + x.at, x.src, x.len};
-          continue;
-        }
-        if (x.d0) cs[ncs++] = {h + x.at, x.src, x.d0};
-        if (x.d1 < x.len) cs[ncs++] = {h + x.at + x.d1, x.src + x.d1, x.len - x.d1};
-      }
-      par_memcpy_spans(cs, ncs);
-      if (part >= ln.part_ready.size()) {
-        hipEvent_t ev;
-        hipError_t ce = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-        if (ce != hipSuccess) { set_error("hipEventCreate", ce); return TMV_ERR_NO_DEVICE; }
-        ln.part_ready.push_back(ev);
-      }
-      hipEvent_t ev = ln.part_ready[part++];
-      hipError_t ce;
-      auto h2d = [&](size_t at, const void *src, size_t len) -> bool {
-        if (!len) return true;
-        if ((ce = hipMemcpyAsync(dd + at, src, len, hipMemcpyHostToDevice, ln.copy)) != hipSuccess) {
-          set_error("hipMemcpyAsync(H2D)", ce);
-          return false;
-        }
-        ctx->m_h2d += len;
-        return true;
-      };
-      if (!h2d(L.off + 4ull * a, h + L.off + 4ull * a, 4ull * (b - a + 1))) return TMV_ERR_LAUNCH;
-      for (int k = 0; k < 4; k++) {
-        const Span &x = sp[k];
-        bool ok;
-        if (x.d1 == 0) {
-          ok = h2d(x.at, h + x.at, x.len);
-        } else {  // staged head, the locked middle (one DMA per locked range), staged tail
-          const size_t cut = x.cut;
-          ok = h2d(x.at, h + x.at, x.d0) && h2d(x.at + x.d0, x.src + x.d0, cut - x.d0) &&
-               h2d(x.at + cut, x.src + cut, x.d1 - cut) && h2d(x.at + x.d1, h + x.at + x.d1, x.len - x.d1);
-        }
-        if (!ok) return TMV_ERR_LAUNCH;
-      }
-      if ((ce = hipEventRecord(ev, ln.copy)) != hipSuccess) {
-        set_error("part event", ce);
-        return TMV_ERR_LAUNCH;
-      }
-      *ready = ev;
-      return 0;
-    };
-    tm.mark("stage", n);
-    const int rc =
-        mixed_stream
-            ? mixed_check_streamed(d, o, kind + lo, dd + kind_at, dd + L.pk, dd + L.sig, dd + L.msg,
-                                   reinterpret_cast<const uint32_t *>(dd + L.off), n,
-                                   static_cast<uint8_t *>(ln.d_out.ptr), ln.stream, ln.helper,
-                                   ln.join, ln.part_split, feed)
-            : batch_check(d, o, sr, dd + L.pk, dd + L.sig, dd + L.msg, reinterpret_cast<const uint32_t *>(dd + L.off), n,
-                          static_cast<uint8_t *>(ln.d_out.ptr), ln.stream, &feed, g_stream_two ? ln.helper : nullptr,
-                          g_stream_two ? ln.join : nullptr);
-    // an error after parts were enqueued: they still use the lane's buffers
-    // and the caller's registered pages, so drain before returning
-    auto drain = [&](int r) {
-      const bool drained = wait_stream(d, ln.copy) == hipSuccess;
-      if (ln.helper) (void)wait_stream(d, ln.helper);
-      if (wait_stream(d, ln.stream) == hipSuccess && drained) ln.unpin();
-      else ln.pinned.clear();  // copies may be in flight: leave the pages registered (see run_batch)
-      return r;
-    };
-    if (rc != 0) return drain(rc);
-    if (tm.on) fprintf(stderr, "[tmv_engine] pinning %9.3f ms (%zu ranges)\n", pin_ms, ln.pinned.size());
-    tm.mark("parts staged + launched", n);
-    // statuses through the lane's staging (a late DMA after a device
-    // timeout must not land in caller memory the call no longer owns)
-    if ((e = hipMemcpyAsync(ln.h_out.ptr, ln.d_out.ptr, n, hipMemcpyDeviceToHost, ln.stream)) != hipSuccess) {
-      set_error("hipMemcpyAsync(D2H)", e);
-      return drain(TMV_ERR_LAUNCH);
-    }
-    ctx->m_d2h += n;
-    return 0;
-  }
-  const uint32_t G = merged ? o.p.groups : 0;
-  const size_t kind_at = L.total;
-  const size_t votes_at = L.total + (sch == Scheme::Mixed ? align16(n) : 0) + (cached ? align16(4ull * n) : 0);
-  const VoteExtStage xp = vote_ext_plan(vs ? vs->ext : nullptr, lo, hi, 0);  // vote / extension entries of the chunk
-  const size_t tab_at = votes_at + (vs ? align16(sizeof(tmv_vote) * xp.nv) : 0);
-  const VoteExtStage xe = vote_ext_plan(vs ? vs->ext : nullptr, lo, hi, tab_at + (vs ? align16(vs->tab_bytes) : 0));
-  const size_t runs_at = xe.end;
-  const size_t run_cap = (size_t)distinct + G;  // key segments cut at group edges
-  const size_t order_at = runs_at + align16(4ull * (2 * run_cap + 1 + G + 1));
-  const size_t total = merged ? order_at + align16(4ull * n) : runs_at;
-  if ((e = ln.h_in.ensure(total, true)) != hipSuccess) { set_error("hipHostMalloc", e); return TMV_ERR_NOMEM; }
-  if ((e = ln.d_in.ensure(total, false)) != hipSuccess) { set_error("hipMalloc", e); return TMV_ERR_NOMEM; }
-  if ((e = ln.h_out.ensure(n, true)) != hipSuccess) { set_error("hipHostMalloc", e); return TMV_ERR_NOMEM; }
-  if ((e = ln.d_out.ensure(n, false)) != hipSuccess) { set_error("hipMalloc", e); return TMV_ERR_NOMEM; }
-  uint8_t *h = static_cast<uint8_t *>(ln.h_in.ptr);
-  uint32_t *off = reinterpret_cast<uint32_t *>(h + L.off);
-  const uint32_t base = msg_off[lo];
-  par_memcpy(h + L.pk, pk + 32ull * lo, 32ull * n);
-  par_memcpy(h + L.sig, sig + 64ull * lo, 64ull * n);
-  for (uint32_t i = 0; i <= n; i++) off[i] = msg_off[lo + i] - base;
-  if (vs) {
-    if (xe.nv) par_memcpy(h + votes_at, vs->votes + lo, sizeof(tmv_vote) * xe.nv);
-    std::memcpy(h + tab_at, vs->tab, vs->tab_bytes);
-    if (vs->ext) vote_ext_stage(*vs->ext, xe, h);
-  } else if (mbytes) {
-    par_memcpy(h + L.msg, msg + base, mbytes);
-  }
-  if (sch == Scheme::Mixed) std::memcpy(h + kind_at, kind + lo, n);
-  if (cached) std::memcpy(h + kind_at, d.slots.data(), 4ull * n);
-  uint32_t n_runs = 0;
-  if (merged) {
-    // key order of the work slots: stable counting sort, chunks scattered in parallel
-    uint32_t *hist = d.key_count.data();
-    std::vector<uint32_t> key_start(kc + 1);
-    uint32_t run = 0;
-    for (uint32_t k = 0; k < kc; k++) {
-      key_start[k] = run;
-      for (uint32_t c = 0; c < kSortChunks; c++) {
-        const uint32_t v = hist[(size_t)c * kc + k];
-        hist[(size_t)c * kc + k] = run;
-        run += v;
-      }
-    }
-    key_start[kc] = run;
-    uint32_t *order = reinterpret_cast<uint32_t *>(h + order_at);
-    const uint32_t *sl = d.slots.data();
-    tmh::parallel_for_n(kSortChunks, kSortChunks, [&](size_t c) {
-      const uint32_t j0 = (uint32_t)((uint64_t)n * c / kSortChunks), j1 = (uint32_t)((uint64_t)n * (c + 1) / kSortChunks);
-      uint32_t *cur = hist + c * kc;
-      for (uint32_t j = j0; j < j1; j++) order[cur[sl[j]]++] = j;
-    });
-    // runs: key segments [key_start[k], key_start[k+1]) cut at group edges
-    uint32_t *rlo = reinterpret_cast<uint32_t *>(h + runs_at);
-    uint32_t *rslot = rlo + run_cap + 1;
-    uint32_t *rg0 = rslot + run_cap;
-    const uint32_t m = o.p.m();
-    uint32_t g = 0;
-    for (uint32_t k = 0; k < kc; k++) {
-      uint32_t a0 = key_start[k];
-      const uint32_t a1 = key_start[k + 1];
-      while (a0 < a1) {
-        while (g < G && (g << o.p.m_log2) <= a0) rg0[g++] = n_runs;
-        rlo[n_runs] = a0;
-        rslot[n_runs] = k;
-        n_runs++;
-        a0 = std::min(a1, (a0 / m + 1) * m);
-      }
-    }
-    while (g < G) rg0[g++] = n_runs;
-    rlo[n_runs] = n;
-    rg0[G] = n_runs;
-  }
-  tm.mark("stage", n);
-  // Small key-cached batches (the VerifyCommit latency path) skip both
-  // copies: the fused kernel reads the pinned staging and writes the
-  // statuses to pinned memory over PCIe (coherent host memory).
-  const bool zero_copy = g_zero_copy && cached && !merged && !vs && n <= g_cached_fused_max && ln.h_in.dev &&
-                         ln.h_out.dev;
-  uint8_t *dd = static_cast<uint8_t *>(zero_copy ? ln.h_in.dev : ln.d_in.ptr);
-  const uint32_t *doff = reinterpret_cast<uint32_t *>(dd + L.off);
-  if (zero_copy) {
-    // inputs are read in place
-  } else if (vs) {  // everything but the message region, which the device writes
-    if ((e = hipMemcpyAsync(dd, h, L.msg, hipMemcpyHostToDevice, ln.stream)) != hipSuccess ||
-        (e = hipMemcpyAsync(dd + L.total, h + L.total, total - L.total, hipMemcpyHostToDevice, ln.stream)) !=
-            hipSuccess) {
-      set_error("hipMemcpyAsync(H2D)", e);
-      return TMV_ERR_LAUNCH;
-    }
-    ctx->m_h2d += L.msg + (total - L.total);
-    const tmv::VoteTab *tab = reinterpret_cast<const tmv::VoteTab *>(dd + tab_at);
-    if ((e = tmv::launch_vote_signbytes(reinterpret_cast<const tmv_vote *>(dd + votes_at), tab,
-                                        dd + tab_at + vs->blob_at, doff, xe.nv, dd + L.msg, ln.stream)) != hipSuccess) {
-      set_error("k_vote_signbytes", e);
-      return TMV_ERR_LAUNCH;
-    }
-    if (vs->ext && (e = vote_ext_launch(*vs->ext, xe, dd, doff, dd + L.msg, ln.stream)) != hipSuccess) {
-      set_error("k_vote_ext_signbytes", e);
-      return TMV_ERR_LAUNCH;
-    }
-  } else if ((e = hipMemcpyAsync(ln.d_in.ptr, h, total, hipMemcpyHostToDevice, ln.stream)) != hipSuccess) {
-    set_error("hipMemcpyAsync(H2D)", e);
-    return TMV_ERR_LAUNCH;
-  } else {
-    ctx->m_h2d += total;
-  }
-  uint8_t *out = static_cast<uint8_t *>(zero_copy ? ln.h_out.dev : ln.d_out.ptr);
-  const uint32_t *dslots = reinterpret_cast<const uint32_t *>(dd + kind_at);
-  int rc;
-  switch (sch) {
-    case Scheme::Ed25519:
-      rc = launch_ed25519(d, o, dd + L.pk, dd + L.sig, dd + L.msg, doff, n, out, ln.stream);
-      break;
-    case Scheme::Sr25519:
-      rc = launch_sr25519(d, o, dd + L.pk, dd + L.sig, dd + L.msg, doff, n, reinterpret_cast<int8_t *>(out), ln.stream);
-      break;
-    case Scheme::Ed25519Cached:
-    case Scheme::Sr25519Cached:
-      if (merged) {
-        const uint32_t *rlo = reinterpret_cast<const uint32_t *>(dd + runs_at);
-        const tmv::KeyRuns runs{rlo, rlo + run_cap + 1, rlo + 2 * run_cap + 1,
-                                reinterpret_cast<const uint32_t *>(dd + order_at), n_runs};
-        rc = launch_key_merged(d, o, sr, dd + L.pk, dd + L.sig, dd + L.msg, doff, dslots, runs, n, out, ln.stream);
-      } else {
-        rc = launch_cached(d, sr, dd + L.pk, dd + L.sig, dd + L.msg, doff, dslots, n, out, ln.stream);
-      }
-      break;
-    default:
-      rc = launch_mixed(d, o, dd + kind_at, dd + L.pk, dd + L.sig, dd + L.msg, doff, n, reinterpret_cast<int8_t *>(out),
-                        ln.stream);
-  }
-  if (rc != 0) return rc;
-  if (zero_copy) return 0;
-  if ((e = hipMemcpyAsync(ln.h_out.ptr, ln.d_out.ptr, n, hipMemcpyDeviceToHost, ln.stream)) != hipSuccess) {
-    set_error("hipMemcpyAsync(D2H)", e);
-    return TMV_ERR_LAUNCH;
-  }
-  ctx->m_d2h += n;
-  return 0;
+      o.batch_eq && n > g_stream_first)
+    return stage_streamed(c, o, sr, mixed_stream, tm);
+  return stage_whole(c, o, sch, merged, distinct, tm);
 }
 
 // Entries per streamed mixed chunk.  mixed_check_streamed carves both
@@ -2299,7 +2310,7 @@ static int run_batch(tmv_ctx *ctx, Scheme sch, const uint8_t *kind, const uint8_
         (void)hipSetDevice(d.id);
         std::lock_guard<std::mutex> lk(d.mu);  // key cache, device scratch, workspaces
         if (d.faulted) return faulted_rc(d);
-        const int r = stage_and_launch(ctx, flags, d, ln, sch, kind, pk, sig, msg, msg_off, c0, c1, vs);
+        const int r = launch_chunk(ctx, flags, d, ln, sch, kind, pk, sig, msg, msg_off, c0, c1, vs);
         if (r == 0) {
           ln.lo = c0;
           ln.n = c1 - c0;
@@ -2358,6 +2369,55 @@ static Device *find_device(tmv_ctx *ctx, int device) {
   for (auto &d : ctx->devs)
     if (d->id == device) return d.get();
   return nullptr;
+}
+
+// What a device-pointer entry point does before it launches, in two steps
+// with the entry point's own argument checks between them; each returns 0 or
+// the entry point's return code with the error text set.
+namespace {
+struct DeviceCall {
+  Device *d = nullptr;
+  hipStream_t s = nullptr;  // the caller's, else the context's own for the device
+  LaunchOpts o;
+  std::unique_lock<std::mutex> lk;  // the device's lock, held until the object goes
+
+  int find(tmv_ctx *ctx, int device) {
+    if (!(d = find_device(ctx, device))) { set_error("device not in context"); return TMV_ERR_ARG; }
+    return d->faulted ? faulted_rc(*d) : 0;
+  }
+  int open(tmv_ctx *ctx, void *stream, uint32_t flags, uint32_t n, bool ed_only) {
+    const int rc = use_device(*d, stream, &s);
+    if (rc != 0) return rc;
+    o = make_opts(ctx, flags, n, false, ed_only);
+    if (o.err) return o.err;
+    ctx->count_call(n);
+    lk = std::unique_lock<std::mutex>(d->mu);
+    return 0;
+  }
+};
+}  // namespace
+
+// One device-resident batch of one kind or mixed: the body of
+// tmv_verify_batch_device_ex, which alone checks its kind arguments, and of
+// its two special cases.
+static int verify_batch_device(tmv_ctx *ctx, int device, uint8_t key_kind, uint32_t flags, bool check_kind,
+                               const uint8_t *d_kind, const uint8_t *d_pk, const uint8_t *d_sig,
+                               const uint8_t *d_msg, const uint32_t *d_msg_off, uint32_t n, int8_t *d_status,
+                               void *stream) {
+  DeviceCall c;
+  int rc = c.find(ctx, device);
+  if (rc != 0) return rc;
+  if (n == 0) return TMV_NOT_ALL;
+  if (check_kind) {
+    if (key_kind == TMV_KIND_MIXED && !d_kind) { set_error("mixed batch without kinds"); return TMV_ERR_ARG; }
+    if (key_kind > TMV_KIND_MIXED) { set_error("unsupported key kind"); return TMV_ERR_ARG; }
+  }
+  if ((rc = c.open(ctx, stream, flags, n, key_kind == TMV_KIND_ED25519)) != 0) return rc;
+  uint8_t *out = reinterpret_cast<uint8_t *>(d_status);
+  if (key_kind == TMV_KIND_ED25519) rc = launch_ed25519(*c.d, c.o, d_pk, d_sig, d_msg, d_msg_off, n, out, c.s);
+  else if (key_kind == TMV_KIND_SR25519) rc = launch_sr25519(*c.d, c.o, d_pk, d_sig, d_msg, d_msg_off, n, d_status, c.s);
+  else rc = launch_mixed(*c.d, c.o, d_kind, d_pk, d_sig, d_msg, d_msg_off, n, d_status, c.s);
+  return rc != 0 ? rc : TMV_NOT_ALL;
 }
 
 extern "C" {
@@ -2431,15 +2491,14 @@ int64_t tmv_vote_sign_bytes_device(tmv_ctx *ctx, const tmv_vote_template *tmpl, 
   Device &d = *ctx->devs[0];
   std::lock_guard<std::mutex> lk(d.mu);
   if (d.faulted) return faulted_rc(d);
-  hipError_t e = hipSetDevice(d.id);
-  if (e != hipSuccess) { set_error("hipSetDevice", e); return TMV_ERR_NO_DEVICE; }
+  hipStream_t s;
+  int rc = use_device(d, nullptr, &s);
+  if (rc != 0) return rc;
   const size_t v_at = 0, t_at = align16(sizeof(tmv_vote) * n), o_at = t_at + align16(tab.size()),
                m_at = o_at + align16(4ull * (n + 1)), bytes = m_at + std::max<size_t>(total, 1);
-  hipStream_t s = context_stream(d);
-  if (!s) { set_error("hipStreamCreate failed"); return TMV_ERR_NO_DEVICE; }
   uint8_t *dev = nullptr;
+  hipError_t e;
   if ((e = hipMalloc(&dev, bytes)) != hipSuccess) { set_error("hipMalloc", e); return TMV_ERR_NOMEM; }
-  int rc = 0;
   if ((e = hipMemcpyAsync(dev + v_at, votes, sizeof(tmv_vote) * n, hipMemcpyHostToDevice, s)) != hipSuccess ||
       (e = hipMemcpyAsync(dev + t_at, tab.data(), tab.size(), hipMemcpyHostToDevice, s)) != hipSuccess ||
       (e = hipMemcpyAsync(dev + o_at, off.data(), 4ull * (n + 1), hipMemcpyHostToDevice, s)) != hipSuccess ||
@@ -2645,52 +2704,22 @@ int tmv_metrics_reset(tmv_ctx *ctx) {
 int tmv_verify_mixed_batch_device(tmv_ctx *ctx, int device, const uint8_t *d_kind, const uint8_t *d_pk,
                                   const uint8_t *d_sig, const uint8_t *d_msg, const uint32_t *d_msg_off, uint32_t n,
                                   int8_t *d_status, void *stream) {
-  Device *dev = find_device(ctx, device);
-  if (!dev) { set_error("device not in context"); return TMV_ERR_ARG; }
-  if (dev->faulted) return faulted_rc(*dev);
-  if (n == 0) return TMV_NOT_ALL;
-  hipError_t e = hipSetDevice(dev->id);
-  if (e != hipSuccess) { set_error("hipSetDevice", e); return TMV_ERR_NO_DEVICE; }
-  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : context_stream(*dev);
-  if (!s) { set_error("hipStreamCreate failed"); return TMV_ERR_NO_DEVICE; }
-  const LaunchOpts o = make_opts(ctx, 0, n);
-  if (o.err) return o.err;
-  ctx->count_call(n);
-  std::lock_guard<std::mutex> lk(dev->mu);
-  int rc = launch_mixed(*dev, o, d_kind, d_pk, d_sig, d_msg, d_msg_off, n, d_status, s);
-  return rc != 0 ? rc : TMV_NOT_ALL;
+  return verify_batch_device(ctx, device, TMV_KIND_MIXED, 0, false, d_kind, d_pk, d_sig, d_msg, d_msg_off, n, d_status,
+                             stream);
 }
 
 int tmv_verify_batch_device_ex(tmv_ctx *ctx, int device, uint8_t key_kind, uint32_t flags, const uint8_t *d_kind,
                                const uint8_t *d_pk, const uint8_t *d_sig, const uint8_t *d_msg,
                                const uint32_t *d_msg_off, uint32_t n, int8_t *d_status, void *stream) {
-  Device *dev = find_device(ctx, device);
-  if (!dev) { set_error("device not in context"); return TMV_ERR_ARG; }
-  if (dev->faulted) return faulted_rc(*dev);
-  if (n == 0) return TMV_NOT_ALL;
-  if (key_kind == TMV_KIND_MIXED && !d_kind) { set_error("mixed batch without kinds"); return TMV_ERR_ARG; }
-  if (key_kind > TMV_KIND_MIXED) { set_error("unsupported key kind"); return TMV_ERR_ARG; }
-  hipError_t e = hipSetDevice(dev->id);
-  if (e != hipSuccess) { set_error("hipSetDevice", e); return TMV_ERR_NO_DEVICE; }
-  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : context_stream(*dev);
-  if (!s) { set_error("hipStreamCreate failed"); return TMV_ERR_NO_DEVICE; }
-  const LaunchOpts o = make_opts(ctx, flags, n, false, key_kind == TMV_KIND_ED25519);
-  if (o.err) return o.err;
-  ctx->count_call(n);
-  std::lock_guard<std::mutex> lk(dev->mu);
-  uint8_t *out = reinterpret_cast<uint8_t *>(d_status);
-  int rc;
-  if (key_kind == TMV_KIND_ED25519) rc = launch_ed25519(*dev, o, d_pk, d_sig, d_msg, d_msg_off, n, out, s);
-  else if (key_kind == TMV_KIND_SR25519) rc = launch_sr25519(*dev, o, d_pk, d_sig, d_msg, d_msg_off, n, d_status, s);
-  else rc = launch_mixed(*dev, o, d_kind, d_pk, d_sig, d_msg, d_msg_off, n, d_status, s);
-  return rc != 0 ? rc : TMV_NOT_ALL;
+  return verify_batch_device(ctx, device, key_kind, flags, true, d_kind, d_pk, d_sig, d_msg, d_msg_off, n, d_status,
+                             stream);
 }
 
 int tmv_verify_batches_device(tmv_ctx *ctx, int device, uint8_t key_kind, uint32_t flags,
                               const tmv_batch_ref *batches, uint32_t n_batches, void *stream) {
-  Device *dev = find_device(ctx, device);
-  if (!dev) { set_error("device not in context"); return TMV_ERR_ARG; }
-  if (dev->faulted) return faulted_rc(*dev);
+  DeviceCall c;
+  int rc = c.find(ctx, device);
+  if (rc != 0) return rc;
   if (key_kind != TMV_KIND_ED25519 && key_kind != TMV_KIND_SR25519) {
     set_error("tmv_verify_batches_device: key_kind must be ed25519 or sr25519");
     return TMV_ERR_ARG;
@@ -2727,16 +2756,12 @@ int tmv_verify_batches_device(tmv_ctx *ctx, int device, uint8_t key_kind, uint32
     r.msg_base[k + 1] = (uint32_t)M;
   }
   if (N == 0) return TMV_NOT_ALL;
-  hipError_t e = hipSetDevice(dev->id);
-  if (e != hipSuccess) { set_error("hipSetDevice", e); return TMV_ERR_NO_DEVICE; }
-  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : context_stream(*dev);
-  if (!s) { set_error("hipStreamCreate failed"); return TMV_ERR_NO_DEVICE; }
   const uint32_t n = (uint32_t)N;
-  const LaunchOpts o = make_opts(ctx, flags, n, false, key_kind == TMV_KIND_ED25519);
-  if (o.err) return o.err;
-  ctx->count_call(n);
-  std::lock_guard<std::mutex> lk(dev->mu);
-  int rc;
+  if ((rc = c.open(ctx, stream, flags, n, key_kind == TMV_KIND_ED25519)) != 0) return rc;
+  Device *dev = c.d;
+  const hipStream_t s = c.s;
+  const LaunchOpts &o = c.o;
+  hipError_t e;
   Workspace *ws = reserve_work(*dev, n, false, s, &rc, o.batch_eq ? &o.p : nullptr);
   if (!ws) return rc;
   Layout L(n, (size_t)M);
@@ -3053,20 +3078,8 @@ int tmv_ed25519_verify(tmv_ctx *ctx, const uint8_t *pk, const uint8_t *msg, size
 int tmv_ed25519_verify_batch_device(tmv_ctx *ctx, int device, const uint8_t *d_pk, const uint8_t *d_sig,
                                     const uint8_t *d_msg, const uint32_t *d_msg_off, uint32_t n, uint8_t *d_valid,
                                     void *stream) {
-  Device *dev = find_device(ctx, device);
-  if (!dev) { set_error("device not in context"); return TMV_ERR_ARG; }
-  if (dev->faulted) return faulted_rc(*dev);
-  if (n == 0) return TMV_NOT_ALL;
-  hipError_t e = hipSetDevice(dev->id);
-  if (e != hipSuccess) { set_error("hipSetDevice", e); return TMV_ERR_NO_DEVICE; }
-  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : context_stream(*dev);
-  if (!s) { set_error("hipStreamCreate failed"); return TMV_ERR_NO_DEVICE; }
-  const LaunchOpts o = make_opts(ctx, 0, n, false, true);
-  if (o.err) return o.err;
-  ctx->count_call(n);
-  std::lock_guard<std::mutex> lk(dev->mu);
-  int rc = launch_ed25519(*dev, o, d_pk, d_sig, d_msg, d_msg_off, n, d_valid, s);
-  return rc != 0 ? rc : TMV_NOT_ALL;
+  return verify_batch_device(ctx, device, TMV_KIND_ED25519, 0, false, nullptr, d_pk, d_sig, d_msg, d_msg_off, n,
+                             reinterpret_cast<int8_t *>(d_valid), stream);
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // Vote-extension entries of a device-built batch
 // (tmv_verify_votes_and_extensions): included by tmverify_runtime.cpp twice,
-// TMV_VOTE_EXT_PART 1 before stage_and_launch (the staging of a chunk's
+// TMV_VOTE_EXT_PART 1 before stage_whole (the staging of a chunk's
 // extension entries) and 2 after run_batch (the C ABI).
 //
 // A batch holds n_votes vote entries, then n_exts extension entries.  A chunk
@@ -167,13 +167,12 @@ int64_t tmv_vote_extension_sign_bytes_device(tmv_ctx *ctx, const tmv_vote_ext_te
   Device &d = *ctx->devs[0];
   std::lock_guard<std::mutex> lk(d.mu);
   if (d.faulted) return faulted_rc(d);
-  hipError_t e = hipSetDevice(d.id);
-  if (e != hipSuccess) { set_error("hipSetDevice", e); return TMV_ERR_NO_DEVICE; }
-  hipStream_t s = context_stream(d);
-  if (!s) { set_error("hipStreamCreate failed"); return TMV_ERR_NO_DEVICE; }
+  hipStream_t s;
+  int rc = use_device(d, nullptr, &s);
+  if (rc != 0) return rc;
   uint8_t *dev = nullptr;
+  hipError_t e;
   if ((e = hipMalloc(&dev, bytes)) != hipSuccess) { set_error("hipMalloc", e); return TMV_ERR_NOMEM; }
-  int rc = 0;
   if ((e = hipMemcpyAsync(dev, h.data(), m_at, hipMemcpyHostToDevice, s)) != hipSuccess ||
       (e = vote_ext_launch(xs, p, dev, reinterpret_cast<const uint32_t *>(dev + o_at), dev + m_at, s)) !=
           hipSuccess ||

@@ -354,7 +354,7 @@ extern "C" uint32_t commitcheck_stream_parts(uint32_t n, uint32_t m, uint32_t fi
 }
 
 // The runtime's caller-page locking over one span split into parts
-// (host/stream_plan.h, stage_and_launch's feed): span [base, base + len) in
+// (host/stream_plan.h, the runtime's StreamFeeder): span [base, base + len) in
 // parts of the given lengths, page size `page`, the lock attempt number
 // `fail_at` (0-based, < 0: none) failing.  Per part: [d0, d1, cut]; then the
 // locked ranges [r0, r1) in order.  Returns the number of locked ranges

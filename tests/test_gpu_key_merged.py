@@ -144,6 +144,54 @@ def test_repeated_calls_fresh_randomness(ctx):
         assert np.array_equal(st.astype(np.uint8), ref)
 
 
+def _merged_groups_of_64(ctx, b, n_keys):
+    """The key-cached batch equation with groups of 64 on the host path; the status vector, and how many groups
+    failed.  That it ran, and through the key cache: its groups are counted, and every distinct key of the call is
+    a hit or a miss."""
+    ctx.set_batch_options(group_log2=6, stats=True)
+    try:
+        s0, k0 = ctx.batch_stats(), ctx.key_cache_stats()
+        ok, st = ctx.verify_batch_ex(N.TMV_KIND_ED25519, KM, b.pk, b.sig, b.msg, b.off)
+        s1, k1 = ctx.batch_stats(), ctx.key_cache_stats()
+    finally:
+        ctx.set_batch_options()
+    # Two other paths could have run.  The key-cached per-entry path (merging judged not worth it) counts no
+    # groups.  The uncached batch equation runs only when the call has more keys than the cache holds, which three
+    # keys never do; that the keys went through the cache shows in one hit or miss per key.
+    assert s1["groups"] - s0["groups"] == (b.n + 63) // 64
+    assert (k1["hits"] - k0["hits"]) + (k1["misses"] - k0["misses"]) == n_keys
+    assert ok == bool((st == 1).all())
+    return st, s1["failed"] - s0["failed"]
+
+
+@pytest.mark.parametrize("n_keys", [1, 3])
+@pytest.mark.parametrize("n", [65, 129, 200])
+def test_few_keys_across_group_edges(ctx, n, n_keys):
+    """The smallest chunks that take the key-merged form (host/key_order.h: distinct + groups <= n / 2): one key
+    on every entry, so its segment is cut into a run at every group edge, and three keys interleaved, whose
+    segments start and end inside groups."""
+    b = _keyed_batch(n, n_keys, 69 + n + n_keys)
+    st, failed = _merged_groups_of_64(ctx, b, n_keys)
+    assert np.array_equal(st.astype(np.uint8), _ref(b)) and (st == 1).all() and failed == 0
+
+
+@pytest.mark.parametrize("slot", [63, 64], ids=["last-of-run", "first-of-run"])
+@pytest.mark.parametrize("n_keys", [1, 3])
+def test_bad_entry_at_the_ends_of_a_cut_run(ctx, n_keys, slot):
+    """The segment of the key with the lowest cache slot ([0, 200) of one key, the first 66 or 67 work slots of
+    three) crosses the group edge at work slot 64 and is cut there: the entry at the last work slot of the run
+    before the edge, or at the first of the run behind it, is bad.  Which of three keys comes first is the cache's
+    choice, so each key's entry number `slot` is bad, and one of them sits at that work slot.  The vector is the
+    oracle's in the caller's order."""
+    n = 200
+    bad = {k + n_keys * slot for k in range(n_keys)}
+    b = _keyed_batch(n, n_keys, 70 + n_keys + slot, bad=bad)
+    ref = _ref(b)
+    assert not ref[sorted(bad)].any() and ref.sum() == n - n_keys
+    st, failed = _merged_groups_of_64(ctx, b, n_keys)
+    assert np.array_equal(st.astype(np.uint8), ref) and 1 <= failed <= n_keys
+
+
 def test_small_cache_falls_back_uncached():
     """More distinct keys than the cache: the uncached batch equation runs."""
     code = r"""

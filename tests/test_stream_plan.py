@@ -1,5 +1,5 @@
 """Streamed host-buffer chunks (tendermint_amd/csrc/host/stream_plan.h, used
-by the runtime's stage_and_launch / batch_check / mixed_check_streamed): the
+by the runtime's stage_streamed / batch_check / mixed_check_streamed): the
 part schedule (a short first part, parts doubling up to TMV_STREAM_PART,
 group edges for one-kind launches, a part cap for mixed chunks) and the
 caller-page locking (two locked ranges per span, only whole pages inside the
