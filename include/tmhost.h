@@ -472,6 +472,89 @@ typedef struct {
 int tmv_blocks_validate_basic(tmv_ctx *ctx, const tmv_block *blocks, uint32_t n, int32_t *results, char *errs,
                               size_t err_stride, uint8_t *hash_out, uint8_t *has_hash);
 
+/* ---- blocks from their protobuf bytes ---- */
+/* A blocksync peer delivers a block as bytes (bcproto.BlockResponse) and the
+ * block store keeps it as bytes; almost everything Block.ValidateBasic hashes
+ * sits in them verbatim.  tmv_blocks_validate_wire validates a window of
+ * blocks from the bytes: data[block_off[i], block_off[i+1]) is the
+ * tendermint.types.Block message of block i (n + 1 offsets, block_off[0] = 0,
+ * never decreasing).
+ *
+ * The contract.  Hashing received bytes equals the reference's
+ * decode-then-re-encode only for bytes its own Marshal would write, so the
+ * scanner (csrc/host/block_wire.h) accepts exactly the canonical gogoproto
+ * encoding -- ascending field numbers, declared wire types, no unknown
+ * fields, minimal varints, sign-extended int32s, no present zero values, the
+ * nullable = false messages present, lengths inside their parent, timestamps
+ * in the reference's domain -- which is what every Go node writes.  Everything
+ * else is TMV_WIRE_NOT_HANDLED with the first problem in byte order in
+ * reason[i]: the caller decodes that block with the reference and uses
+ * tmv_blocks_validate_basic.  No verdict is ever given on bytes the scanner
+ * did not fully recognise.  Also not handled, on purpose: a non-empty evidence
+ * list (EVIDENCE) and a chain_id with a NUL or a byte >= 0x80 (CHAIN_ID);
+ * LIMIT: a value the view structs cannot hold (a block_id_flag above 255).
+ *
+ * Handled blocks: results[i], the text at errs + i*err_stride, hash_out and
+ * has_hash are exactly what tmv_blocks_validate_basic returns for the block's
+ * view -- same order, same strings.  (The reference's BlockFromProto runs the
+ * header's and the commit's ValidateBasic before Block.ValidateBasic: pass or
+ * fail is the same, which text comes first may differ.  This call reports
+ * Block.ValidateBasic's, which is what validateBlock reports.)  hash_out /
+ * has_hash may be NULL; a block that is not handled has has_hash[i] = 0, an
+ * empty text and zeroed hash.
+ *
+ * A call with at least $TMV_DEVICE_BLOCK_MIN handled blocks (default 32) makes
+ * one tmv_merkle_span_roots call over the caller's bytes (a weak reference):
+ * one upload, one leaf launch and one tree launch for every Commit.Hash,
+ * Data.Hash and Header.Hash of the window.  Smaller calls, and a build without
+ * the engine, hash the views with the host code of tmv_blocks_validate_basic.
+ * A commit that fails Commit.ValidateBasic is not hashed.  A block holding a
+ * transaction longer than $TMV_DEVICE_WIRE_MAX_TX bytes (default 1024, as
+ * $TMV_DEVICE_RESULTS_MAX_DATA; read on every call) has its Data.Hash computed
+ * on the host inside a device call: one lane hashes one leaf.
+ *
+ * part_size != 0: psh_total_out[i] / psh_hash_out + 32*i =
+ * NewPartSetFromData(block i's bytes, part_size).Header() of every block,
+ * handled or not, through tmv_part_set_headers under its own device rule.
+ * part_size == 0: psh_* are not written and may be NULL.
+ *
+ * views_out (may be NULL): the views, to be freed with tmv_block_views_free;
+ * they point into `data`, which must outlive them.
+ * tmv_block_views_block(v, i)->last_commit can go straight into a
+ * tmv_commit_job.  Returns the number of blocks that are not TMV_WIRE_OK, or
+ * < 0 (then *views_out is NULL). */
+#define TMV_WIRE_OK 0          /* Block.ValidateBasic passes */
+#define TMV_WIRE_INVALID 1     /* it fails: text at errs + i*err_stride */
+#define TMV_WIRE_NOT_HANDLED 2 /* reason[i] = TMV_WIRE_REASON_*: decode with the reference, use tmv_blocks_validate_basic */
+
+#define TMV_WIRE_REASON_NONE 0
+#define TMV_WIRE_REASON_TRUNCATED 1     /* a tag, varint or length runs past its enclosing message */
+#define TMV_WIRE_REASON_WIRE_TYPE 2     /* a known field with another wire type */
+#define TMV_WIRE_REASON_UNKNOWN_FIELD 3
+#define TMV_WIRE_REASON_ORDER 4         /* field numbers not ascending, or a scalar twice */
+#define TMV_WIRE_REASON_VARINT 5        /* padded, longer than 10 bytes, beyond 64 bits, or outside its 32-bit type */
+#define TMV_WIRE_REASON_ZERO_PRESENT 6  /* a zero scalar, empty bytes or empty string that is present */
+#define TMV_WIRE_REASON_MISSING 7       /* a nullable = false message is absent */
+#define TMV_WIRE_REASON_TIME 8          /* a timestamp outside the reference's domain */
+#define TMV_WIRE_REASON_EVIDENCE 9      /* a non-empty evidence list */
+#define TMV_WIRE_REASON_CHAIN_ID 10     /* a chain_id with a NUL or a byte >= 0x80 */
+#define TMV_WIRE_REASON_LIMIT 11        /* a value the view structs cannot hold */
+
+typedef struct tmv_block_views tmv_block_views;
+
+int tmv_blocks_validate_wire(tmv_ctx *ctx, const uint8_t *data, const uint32_t *block_off, uint32_t n,
+                             uint32_t part_size /* 0: no part-set headers */,
+                             int32_t *results, int32_t *reason, char *errs, size_t err_stride,
+                             uint8_t *hash_out, uint8_t *has_hash,
+                             uint32_t *psh_total_out, uint8_t *psh_hash_out,
+                             tmv_block_views **views_out /* may be NULL */);
+/* The scanner alone: reason[i] (may be NULL) and the views of n blocks.
+ * Returns the number of blocks that were not handled, or < 0. */
+int tmv_blocks_parse_wire(const uint8_t *data, const uint32_t *block_off, uint32_t n, int32_t *reason,
+                          tmv_block_views **out);
+const tmv_block *tmv_block_views_block(const tmv_block_views *v, uint32_t i); /* NULL for a block that was not handled */
+void tmv_block_views_free(tmv_block_views *v);
+
 /* ---- ABCI results and consensus params (abci/types/types.go, types/params.go) ---- */
 /* Calls with at least $TMV_DEVICE_RESULTS_MIN results (default 4096; DESIGN.md
  * section 21) hash on the device in one tmv_tx_results_hashes call (a weak

@@ -272,6 +272,36 @@ int tmv_tx_results_hashes(tmv_ctx *ctx, uint32_t flags, const uint32_t *code, co
                           const uint32_t *tree_off, uint32_t n_trees, const uint8_t *first, const uint32_t *first_off,
                           uint8_t *root_out);
 
+/* Merkle roots over spans of one buffer: what Block.ValidateBasic hashes lies
+ * in a block's protobuf bytes verbatim (a Commit.Hash leaf is the payload of a
+ * `signatures` entry, a Data.Hash leaf SHA-256 of a `txs` entry, a Header.Hash
+ * leaf a header field's payload behind at most one wrapper tag), so a window
+ * of received blocks is hashed from a table of spans, with no columns packed
+ * (the host layer's tmv_blocks_validate_wire builds the table; DESIGN.md
+ * section 22).
+ * Leaf i is SHA-256(0x00 || [tag] || data[pos, pos + len)): the RFC 6962 leaf
+ * prefix, with TMV_SPAN_TAG one more byte (the low 8 bits of flags, which are
+ * 0 without it), then the span.  With TMV_SPAN_PREHASH it is SHA-256(0x00 ||
+ * SHA-256(span)), as Txs.Hash (types/tx.go:34-39); not together with TAG.
+ * Tree t holds the leaves [tree_off[t], tree_off[t+1]) (tree_off[0] = 0,
+ * tree_off[n_trees] = n_leaves); a tree without leaves hashes to SHA-256("").
+ * Spans may overlap and come in any order.  root_out: n_trees x 32 bytes.
+ * One upload (bytes, spans and offsets), one k_span_leaves launch, one
+ * k_merkle_tree launch, one copy back.  One lane hashes one leaf whatever its
+ * length, so one span of many KiB delays the whole call (the host layer keeps
+ * such blocks' transactions on the host).
+ * TMV_ERR_ARG: null pointers, pos + len > data_len, both flags, an unknown flag
+ * bit (a tag byte without TMV_SPAN_TAG among them), offsets that do not start
+ * at 0, decrease or do not end at n_leaves, more than 2^26 leaves or trees,
+ * more than 2^30 bytes.  n_trees == 0 returns 0.  Synchronous, device 0; 0 or
+ * < 0 on error. */
+typedef struct { uint32_t pos, len, flags; } tmv_leaf_span;
+#define TMV_SPAN_TAG     0x100u /* low 8 bits of flags: one byte hashed between the leaf prefix and the span */
+#define TMV_SPAN_PREHASH 0x200u /* leaf = SHA-256(0x00 || SHA-256(span)), as Txs.Hash; not together with TAG */
+int tmv_merkle_span_roots(tmv_ctx *ctx, const uint8_t *data, uint32_t data_len,
+                          const tmv_leaf_span *leaves, uint32_t n_leaves,
+                          const uint32_t *tree_off, uint32_t n_trees, uint8_t *root_out);
+
 /* Merkle inclusion proofs (crypto/merkle/proof.go).  Blocksync's replay loop
  * builds every block's part set (internal/blocksync/reactor.go:563-582:
  * first.MakePartSet -> NewPartSetFromData, types/part_set.go:172-200 ->
@@ -386,7 +416,8 @@ int tmv_verify_mixed_batch_ex(tmv_ctx *ctx, uint32_t flags, const uint8_t *kind,
  * "k_secp_verify_comb" (secp256k1 with TMV_FLAG_KEY_CACHE), "k_merkle_leaves_long",
  * "k_merkle_leaves", "k_merkle_tree_levels", "k_merkle_aunts" and "k_merkle_verify_proofs" (the launches
  * of tmv_merkle_proofs / tmv_merkle_verify_proofs), "k_merkle_digests_long" and "k_merkle_value_ops"
- * (tmv_merkle_value_ops), "k_commit_leaves" (tmv_commit_hashes), "k_result_leaves" (tmv_tx_results_hashes) -- is bracketed by HIP timing events on the stream it runs on
+ * (tmv_merkle_value_ops), "k_commit_leaves" (tmv_commit_hashes), "k_result_leaves" (tmv_tx_results_hashes),
+ * "k_span_leaves" (tmv_merkle_span_roots) -- is bracketed by HIP timing events on the stream it runs on
  * (process-wide, two event records per launch); 0 turns it off.
  * tmv_kernel_timing_read waits for the recorded launches of `kernel`, returns
  * their summed duration and count, and forgets them.  No reference

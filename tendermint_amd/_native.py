@@ -40,6 +40,7 @@ TMV_MERKLE_LEAF_HASH_GIVEN = 2
 TMV_MERKLE_LONG_LEAVES = 4
 TMV_MERKLE_SHORT_LEAVES = 8
 TMV_RESULTS_FIRST_LEAF = 1
+TMV_SPAN_TAG, TMV_SPAN_PREHASH = 0x100, 0x200  # tmv_leaf_span.flags
 TMV_KIND_MIXED = 2
 TMV_KIND_SECP256K1 = 3  # include/tmhost.h: 33-byte compressed keys, verified signature by signature
 TMV_VOTE_WITH_BLOCK = 0x80000000
@@ -64,7 +65,7 @@ EXPORTS = [
     "tmv_verify_votes", "tmv_vote_sign_bytes_device", "tmv_verify_votes_and_extensions",
     "tmv_vote_extension_sign_bytes_device", "tmv_merkle_roots",
     "tmv_merkle_aunt_offsets", "tmv_merkle_proofs", "tmv_merkle_verify_proofs", "tmv_merkle_value_ops",
-    "tmv_commit_hashes", "tmv_tx_results_hashes",
+    "tmv_commit_hashes", "tmv_tx_results_hashes", "tmv_merkle_span_roots",
     "tmv_kernel_timing", "tmv_kernel_timing_read", "tmv_metrics_read", "tmv_metrics_reset",
     # include/tmhost.h
     "tmv_batch_new", "tmv_batch_add", "tmv_batch_len", "tmv_batch_verify", "tmv_batch_free",
@@ -73,6 +74,7 @@ EXPORTS = [
     "tmv_part_set_headers", "tmv_part_set_proofs", "tmv_parts_verify", "tmv_proofs_verify",
     "tmv_proof_ops_verify", "tmv_tx_proofs_validate",
     "tmv_commit_hash_many", "tmv_blocks_validate_basic",
+    "tmv_blocks_validate_wire", "tmv_blocks_parse_wire", "tmv_block_views_block", "tmv_block_views_free",
     "tmv_results_hash_many", "tmv_consensus_params_hash", "tmv_block_results_verify", "tmv_consensus_params_verify",
     "tmv_vote_extension_sign_bytes", "tmv_vote_extension_template_encode", "tmv_verify_extended_votes",
 ]
@@ -214,6 +216,7 @@ def lib() -> ctypes.CDLL:
         i64p = ctypes.POINTER(ctypes.c_int64)
         L.tmv_tx_results_hashes.argtypes = [vp, ctypes.c_uint32, u32p, i64p, i64p, u8p, u32p, u32p, ctypes.c_uint32,
                                             u8p, u32p, u8p]
+        L.tmv_merkle_span_roots.argtypes = [vp, u8p, ctypes.c_uint32, u32p, ctypes.c_uint32, u32p, ctypes.c_uint32, u8p]
         L.tmv_merkle_verify_proofs.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, i64p, i64p, u8p, u8p, u32p, u8p,
                                                u8p, u32p, i8p, u8p, u8p, u8p]
         L.tmv_merkle_value_ops.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, u8p, u32p, u32p, u8p, u32p, i64p, i64p,
@@ -594,6 +597,33 @@ class Context:
                                                     _p(data_off, ctypes.c_uint32), _p(tree_off, ctypes.c_uint32),
                                                     n_trees, fp, None if fo is None else _p(fo, ctypes.c_uint32),
                                                     _p(out)), "tmv_tx_results_hashes")
+        return out[:n_trees]
+
+    def merkle_span_roots(self, data, spans, tree_off: np.ndarray, data_len=None, n_leaves=None) -> np.ndarray:
+        """Merkle roots over spans of one buffer (tmv_merkle_span_roots):
+        (n_trees, 32) uint8.  data: uint8 array or bytes, or None for a null
+        pointer; spans: (n, 3) uint32 rows of (pos, len, flags) with
+        TMV_SPAN_TAG | tag byte or TMV_SPAN_PREHASH, or None for a null pointer;
+        tree t holds the leaves [tree_off[t], tree_off[t+1]).  data_len /
+        n_leaves override the arrays' sizes."""
+        n_trees = len(tree_off) - 1
+        out = np.zeros((max(n_trees, 1), 32), np.uint8)
+        tree_off = np.ascontiguousarray(tree_off, np.uint32)
+        if data is not None:
+            data = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray)) else np.ascontiguousarray(
+                data, np.uint8)
+            if data_len is None:
+                data_len = len(data)
+            data = data if data.size else np.zeros(1, np.uint8)
+        if spans is not None:
+            spans = np.ascontiguousarray(spans, np.uint32).reshape(-1, 3)
+            if n_leaves is None:
+                n_leaves = len(spans)
+            spans = spans if spans.size else np.zeros((1, 3), np.uint32)
+        self._check(self._lib.tmv_merkle_span_roots(self._h, None if data is None else _p(data), data_len or 0,
+                                                    None if spans is None else _p(spans, ctypes.c_uint32),
+                                                    n_leaves or 0, _p(tree_off, ctypes.c_uint32), n_trees, _p(out)),
+                    "tmv_merkle_span_roots")
         return out[:n_trees]
 
     def merkle_roots(self, data, leaf_off: np.ndarray, tree_off: np.ndarray) -> np.ndarray:

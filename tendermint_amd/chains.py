@@ -340,13 +340,44 @@ def blocksync_replay_full(ctx, chain_id: str, vals: H.ValidatorSet, blocks: List
                              verify_commits, lib, vals_hash, last_block_height, "blocksync_replay_full")
 
 
+def blocksync_replay_wire(ctx, chain_id: str, vals: H.ValidatorSet, raws: List[bytes], last_block_id: H.BlockID,
+                          initial_height: int = 1, window: int = 600, depth: Optional[int] = None,
+                          part_size: int = 65536, verify_commits=None, lib=None, vals_hash: Optional[bytes] = None,
+                          last_block_height: int = 0) -> Tuple[int, Optional[Tuple[int, str]]]:
+    """blocksync_replay_full over the blocks as a peer delivers them: `raws`
+    holds each block's protobuf bytes (bcproto.BlockResponse.block), nothing is
+    decoded by the caller.  The same loop, with Block.ValidateBasic, the block
+    hashes, the part-set headers and the headers and commits that the other
+    checks read all taken from one tmv_blocks_validate_wire call per window
+    (H.blocks_validate_wire: one upload of the window's bytes).  Returns what
+    blocksync_replay_full returns on the decoded blocks.  A block whose bytes
+    the strict scanner hands back ends the replay at its
+    height with "block wire not handled: <reason name>": the reference would
+    decode it and go on, and this model has no Go decoder to fall back to."""
+    return _replay_validated(ctx, chain_id, vals, raws, last_block_id, initial_height, window, depth, part_size,
+                             verify_commits, lib, vals_hash, last_block_height, "blocksync_replay_wire", wire=True)
+
+
+def _wire_window(ctx, lib, raws, part_size, height_before):
+    """One window of blocksync_replay_wire: (decoded blocks, basic, psh) as
+    _replay_validated reads them, a block that was not handled as (height it
+    should have, text) in place of the decoded block."""
+    vs = H.blocks_validate_wire(ctx, raws, part_size, lib, decode=True)
+    blocks, height = [], height_before
+    for v in vs:
+        height = v.block.height if v.block is not None else (height or 0) + 1
+        blocks.append(v.block if v.block is not None else (height, "block wire not handled: " + v.reason))
+    return blocks, [(v.error, v.hash) for v in vs], [v.part_set_header for v in vs]
+
+
 def _replay_validated(ctx, chain_id, vals, blocks, last_block_id, initial_height, window, depth, part_size,
-                      verify_commits, lib, vals_hash, last_block_height, who, stateful=None):
+                      verify_commits, lib, vals_hash, last_block_height, who, stateful=None, wire=False):
     """The replay loop of blocksync_replay_full; with `stateful` (a
     _StatefulChecks) also validateBlock's state-dependent checks, each at its
-    place in the reference's order."""
+    place in the reference's order; with `wire`, `blocks` holds the blocks'
+    protobuf bytes (blocksync_replay_wire)."""
     for b in blocks[:-1]:
-        if b.raw is None:
+        if not wire and b.raw is None:
             raise ValueError("%s: block %d has no raw bytes" % (who, b.height))
     if depth is None:
         depth = 1 if verify_commits else 2
@@ -357,17 +388,29 @@ def _replay_validated(ctx, chain_id, vals, blocks, last_block_id, initial_height
     def run(lo):
         # the previous block rides along: its BlockID is state.LastBlockID of the window's first block
         first_of = max(lo - 1, 0)
-        firsts = blocks[first_of:min(lo + window, len(blocks) - 1)]
-        basic = H.blocks_validate_basic(ctx, firsts, lib)
-        psh = H.part_set_headers(ctx, [b.raw for b in firsts], part_size, lib)
+        end = min(lo + window, len(blocks) - 1)
+        if wire:  # the window's last pair needs its second block decoded as well
+            decoded, basic, psh = _wire_window(ctx, lib, blocks[first_of:end + 1], part_size,
+                                               last_block_height if first_of == 0 else None)
+            firsts = decoded[:-1]
+        else:
+            firsts, decoded = blocks[first_of:end], blocks[first_of:end + 1]
+            basic = H.blocks_validate_basic(ctx, firsts, lib)
+            psh = H.part_set_headers(ctx, [b.raw for b in firsts], part_size, lib)
         before = stateful.window(ctx, lib, first_of, len(firsts)) if stateful else None
         ids = [H.BlockID(hash_ or b"", total, phash) for (_, hash_), (total, phash) in zip(basic, psh)]
         out, jobs, slots = [], [], []
         for i in range(lo - first_of, len(firsts)):
-            first, second = firsts[i], blocks[first_of + i + 1]
+            first, second = firsts[i], decoded[i + 1]
             g = first_of + i
+            unhandled = first if isinstance(first, tuple) else second if isinstance(second, tuple) else None
+            if unhandled is not None:  # wire only: ends the replay
+                out.append(unhandled[0])
+                slots.append((None, unhandled[1], None, None))
+                break
             state_last = ids[i - 1] if g > 0 else last_block_id
-            state_height = blocks[g - 1].height if g > 0 else last_block_height
+            prev = firsts[i - 1] if g > 0 else None  # a tuple: not handled, and an earlier window has said so
+            state_height = last_block_height if prev is None else prev[0] if isinstance(prev, tuple) else prev.height
             hd = first.header
             err = basic[i][0]
             if err is None and stateful:
@@ -404,7 +447,8 @@ def _replay_validated(ctx, chain_id, vals, blocks, last_block_id, initial_height
             out.append(hd.height)
             slots.append((light, err, full, late))
         res = check(jobs)
-        return [(h, res[light] or err or (res[full] if full is not None else None) or late)
+        return [(h, (res[light] if light is not None else None) or err or
+                 (res[full] if full is not None else None) or late)
                 for h, (light, err, full, late) in zip(out, slots)]
 
     applied = 0

@@ -23,6 +23,7 @@
 
 #include "../../../include/tmhost.h"
 #include "../../../include/tmverify.h"
+#include "block_common.h"
 #include "commit_encode.h"
 #include "tm_host_internal.h"
 #include "tm_light.h"
@@ -42,98 +43,11 @@ extern "C" int tmv_header_hashes(tmv_ctx *ctx, const tmv_header *headers, uint32
 
 namespace {
 
-using tmh::Bytes;
-using tmh::Digest;
+using namespace tmh_block;
 using tmh_internal::parallel_for;
 
 constexpr uint64_t kEngineMaxItems = 1ull << 26;  // signatures / leaves per engine call
 constexpr uint64_t kEngineMaxBytes = 1ull << 30;  // leaf bytes per engine call
-
-// Calls that hash fewer commits (tmv_commit_hash_many) or validate fewer blocks
-// (tmv_blocks_validate_basic) than this compute on the host: no launch on the
-// latency path of a single block.  32 is tmv_header_hashes' rule; DESIGN.md
-// section 16 has the sweep.  TMV_DEVICE_BLOCK_MIN overrides (read on every
-// call: tests change it).
-uint32_t device_block_min() {
-  const char *e = std::getenv("TMV_DEVICE_BLOCK_MIN");
-  return e ? (uint32_t)std::strtoul(e, nullptr, 10) : 32u;
-}
-
-void put(char *errs, size_t stride, size_t i, const std::string &s) {
-  if (!errs || !stride) return;
-  char *o = errs + i * stride;
-  const size_t m = std::min(s.size(), stride - 1);
-  std::memcpy(o, s.data(), m);
-  o[m] = 0;
-}
-
-void digest_out(const Digest &dg, uint8_t out[32]) {
-  for (int i = 0; i < 8; i++)
-    for (int b = 0; b < 4; b++) out[4 * i + b] = (uint8_t)(dg.w[i] >> (24 - 8 * b));
-}
-
-void empty_hash(uint8_t out[32]) {  // merkle emptyHash(): SHA-256("")
-  Digest e;
-  tmh::Sha256Bytes(e.w, nullptr, 0, nullptr, 0);
-  digest_out(e, out);
-}
-
-tmh::ByteView view(const tmv_bytes &b) { return tmh::ByteView(b.p, b.len); }
-Bytes copy(const uint8_t *p, size_t n) { return p && n ? Bytes(p, p + n) : Bytes(); }
-
-tmh::BlockID block_id_of(const tmv_block_id &b) {
-  tmh::BlockID r;
-  r.hash = copy(b.hash, b.hash_len);
-  r.part_set_header.total = b.psh_total;
-  r.part_set_header.hash = copy(b.psh_hash, b.psh_hash_len);
-  return r;
-}
-
-tmh::Header header_of(const tmv_header &h) {
-  tmh::Header o;
-  o.version_block = h.version_block;
-  o.version_app = h.version_app;
-  o.chain_id = h.chain_id ? h.chain_id : "";
-  o.height = h.height;
-  o.time = tmh::Timestamp{h.time_seconds, h.time_nanos};
-  o.last_block_id = block_id_of(h.last_block_id);
-  o.last_commit_hash = view(h.last_commit_hash);
-  o.data_hash = view(h.data_hash);
-  o.validators_hash = view(h.validators_hash);
-  o.next_validators_hash = view(h.next_validators_hash);
-  o.consensus_hash = view(h.consensus_hash);
-  o.app_hash = view(h.app_hash);
-  o.last_results_hash = view(h.last_results_hash);
-  o.evidence_hash = view(h.evidence_hash);
-  o.proposer_address = view(h.proposer_address);
-  return o;
-}
-
-tmh::Error commit_validate_basic(const tmv_commit &c) {  // the parts Commit.ValidateBasic reads
-  tmh::Commit o;
-  o.height = c.height;
-  o.round = c.round;
-  o.block_id = block_id_of(c.block_id);
-  o.signatures.resize(c.n_sigs);
-  for (uint32_t i = 0; i < c.n_sigs; i++) {
-    const tmv_commit_sig &s = c.sigs[i];
-    tmh::CommitSig &d = o.signatures[i];
-    d.block_id_flag = (tmh::BlockIDFlag)s.block_id_flag;
-    d.validator_address = tmh::ByteView(s.validator_address, s.validator_address_len);
-    d.timestamp = tmh::Timestamp{s.ts_seconds, s.ts_nanos};
-    d.signature = tmh::ByteView(s.signature, s.signature_len);
-  }
-  return tmh::CommitValidateBasic(o);
-}
-
-bool commit_pointers_ok(const tmv_commit &c) {
-  if (c.n_sigs && !c.sigs) return false;
-  for (uint32_t i = 0; i < c.n_sigs; i++)
-    if ((c.sigs[i].validator_address_len && !c.sigs[i].validator_address) ||
-        (c.sigs[i].signature_len && !c.sigs[i].signature))
-      return false;
-  return true;
-}
 
 bool engine_accepts(const tmv_commit &c) {  // tmv_commit_hashes' fixed columns
   for (uint32_t i = 0; i < c.n_sigs; i++) {
@@ -184,26 +98,6 @@ int commit_hashes(tmv_ctx *ctx, const std::vector<const tmv_commit *> &cs, uint8
     lo = hi;
   }
   return 0;
-}
-
-// merkle.HashFromByteSlices over items, each hashed first when prehash
-// (Txs.Hash, types/tx.go:34-39), on the host.
-void items_root_host(const tmv_bytes *items, uint32_t n, bool prehash, uint8_t out[32]) {
-  if (n == 0) return empty_hash(out);
-  static const uint8_t zero = 0;
-  std::vector<Digest> lv(n);
-  for (uint32_t i = 0; i < n; i++) {
-    if (prehash) {
-      Digest t;
-      uint8_t tb[32];
-      tmh::Sha256Bytes(t.w, nullptr, 0, items[i].p, items[i].len);
-      digest_out(t, tb);
-      tmh::Sha256Bytes(lv[i].w, &zero, 1, tb, 32);
-    } else {
-      tmh::Sha256Bytes(lv[i].w, &zero, 1, items[i].p, items[i].len);
-    }
-  }
-  digest_out(tmh::MerkleRootHostRange(lv.data(), n), out);
 }
 
 // One list of byte strings per block (transactions or evidence).
@@ -260,13 +154,6 @@ int list_roots(tmv_ctx *ctx, const Lists &ls, const std::vector<uint32_t> &who, 
   return 0;
 }
 
-std::string wrong_hash(const char *field, const uint8_t want[32], const tmv_bytes &got) {
-  return std::string("wrong Header.") + field + ". Expected " + tmh::HexUpper(want, 32) + ", got " +
-         tmh::HexUpper(got.p, got.len);
-}
-
-bool same(const uint8_t want[32], const tmv_bytes &got) { return got.len == 32 && std::memcmp(want, got.p, 32) == 0; }
-
 }  // namespace
 
 extern "C" {
@@ -313,12 +200,7 @@ int tmv_blocks_validate_basic(tmv_ctx *ctx, const tmv_block *blocks, uint32_t n,
   // Header.ValidateBasic, nil LastCommit, Commit.ValidateBasic
   std::vector<tmh::Header> hs(n);
   std::vector<std::string> text(n);
-  parallel_for(n, 16, [&](size_t b) {
-    hs[b] = header_of(blocks[b].header);
-    if (tmh::Error e = tmh::HeaderValidateBasic(hs[b])) text[b] = "invalid header: " + *e;
-    else if (!blocks[b].last_commit) text[b] = "nil LastCommit";
-    else if (tmh::Error ce = commit_validate_basic(*blocks[b].last_commit)) text[b] = "wrong LastCommit: " + *ce;
-  });
+  parallel_for(n, 16, [&](size_t b) { text[b] = checks_before_hashes(blocks[b], &hs[b]); });
 
   // Header.Hash of every header as given
   if (hash_out) {
@@ -360,9 +242,7 @@ int tmv_blocks_validate_basic(tmv_ctx *ctx, const tmv_block *blocks, uint32_t n,
     const tmv_header &h = blocks[b].header;
     const uint8_t *ch = commit_hash.data() + 32ull * k, *dh = data_hash.data() + 32ull * b,
                   *eh = evidence_hash.data() + 32ull * b;
-    if (!same(ch, h.last_commit_hash)) text[b] = wrong_hash("LastCommitHash", ch, h.last_commit_hash);
-    else if (!same(dh, h.data_hash)) text[b] = wrong_hash("DataHash", dh, h.data_hash);
-    else if (!same(eh, h.evidence_hash)) text[b] = wrong_hash("EvidenceHash", eh, h.evidence_hash);
+    text[b] = compare_hashes(h, ch, dh, eh);
   }
 
   int failed = 0;

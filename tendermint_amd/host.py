@@ -388,7 +388,10 @@ class PreparedJobs:
                     vcache[key] = _c_validators(k, jb.vals)
                 cv, nv, prop = vcache[key], len(jb.vals.validators), jb.vals.proposer_index
             cc = None
-            if jb.commit is not None:
+            if isinstance(jb.commit, ViewCommit):  # already a tmv_commit, inside a tmv_block_views object
+                cc = jb.commit.ptr
+                k.refs.append(jb.commit.owner)
+            elif jb.commit is not None:
                 key = id(jb.commit)
                 if key not in ccache:
                     ccache[key] = _c_commit(k, jb.commit)
@@ -1236,6 +1239,178 @@ def blocks_validate_basic(ctx, blocks: List[FullBlock], lib=None) -> List[Tuple[
     Header.Hash of the header as given, which is Block.Hash() of a block that
     passes, or None where the reference returns nil)."""
     return PreparedBlocks(blocks).run(ctx, lib)
+
+
+# ---------------------------------------------------------------- blocks from their protobuf bytes
+# tmv_blocks_validate_wire / tmv_blocks_parse_wire (include/tmhost.h; DESIGN.md section 22).
+
+WIRE_OK, WIRE_INVALID, WIRE_NOT_HANDLED = 0, 1, 2
+WIRE_REASONS = ("NONE", "TRUNCATED", "WIRE_TYPE", "UNKNOWN_FIELD", "ORDER", "VARINT", "ZERO_PRESENT", "MISSING",
+                "TIME", "EVIDENCE", "CHAIN_ID", "LIMIT")
+
+
+@dataclass
+class WireVerdict:
+    """One block of tmv_blocks_validate_wire.  result: WIRE_OK / WIRE_INVALID
+    (error: Block.ValidateBasic's text) / WIRE_NOT_HANDLED (reason: a name of
+    WIRE_REASONS).  hash: Header.Hash of a handled block (None where the
+    reference returns nil); part_set_header: (total, hash), or None without a
+    part size; block: the decoded view of a handled block, when asked for."""
+    result: int
+    reason: str = "NONE"
+    error: Optional[str] = None
+    hash: Optional[bytes] = None
+    part_set_header: Optional[Tuple[int, bytes]] = None
+    block: Optional[FullBlock] = None
+
+
+def _setup_block_wire(L):
+    if not getattr(L, "_tmhost_block_wire", False):
+        u32p, i32p = ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int32)
+        L.tmv_blocks_validate_wire.argtypes = [ctypes.c_void_p, _u8p, u32p, ctypes.c_uint32, ctypes.c_uint32, i32p,
+                                               i32p, ctypes.c_char_p, ctypes.c_size_t, _u8p, _u8p, u32p, _u8p,
+                                               ctypes.POINTER(ctypes.c_void_p)]
+        L.tmv_blocks_parse_wire.argtypes = [_u8p, u32p, ctypes.c_uint32, i32p, ctypes.POINTER(ctypes.c_void_p)]
+        L.tmv_block_views_block.restype = ctypes.POINTER(CBlock)
+        L.tmv_block_views_block.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
+        L.tmv_block_views_free.restype = None
+        L.tmv_block_views_free.argtypes = [ctypes.c_void_p]
+        L._tmhost_block_wire = True
+    return L
+
+
+class WireWindow:
+    """The bytes of a list of serialised blocks in one buffer with their
+    offsets (data, block_off), as tmv_blocks_validate_wire takes them."""
+
+    def __init__(self, raws: List[bytes]):
+        self.n = n = len(raws)
+        blob = b"".join(raws)
+        self.data = (ctypes.c_uint8 * max(1, len(blob))).from_buffer_copy(blob or b"\0")
+        self.off = (ctypes.c_uint32 * (n + 1))()
+        at = 0
+        for i, r in enumerate(raws):
+            at += len(r)
+            self.off[i + 1] = at
+        self.raws = raws
+
+
+def _take(p, n: int) -> bytes:
+    return ctypes.string_at(p, n) if n else b""
+
+
+def _py_block_id(b: CBlockID) -> BlockID:
+    return BlockID(_take(b.hash, b.hash_len), b.psh_total, _take(b.psh_hash, b.psh_hash_len))
+
+
+class _ViewsOwner:
+    """A tmv_block_views object and the bytes it points into, freed with the
+    last Python object that refers to them."""
+
+    def __init__(self, L, handle, window: WireWindow):
+        self.L, self.handle, self.window = L, handle, window
+
+    def __del__(self):
+        self.L.tmv_block_views_free(self.handle)
+
+
+class ViewCommit:
+    """The last commit of a block decoded by tmv_blocks_validate_wire, left
+    where it is: a tmv_commit inside a tmv_block_views object.  PreparedJobs
+    passes it to tmv_verify_commits by pointer, so a window's signatures are
+    never turned into Python objects and back; read as a Commit (height, round,
+    block_id, signatures, ==) it is decoded on first use."""
+
+    def __init__(self, ptr, owner: _ViewsOwner):
+        self.ptr, self.owner, self._commit = ptr, owner, None
+
+    def decoded(self) -> Commit:
+        if self._commit is None:
+            lc = self.ptr.contents
+            self._commit = Commit(lc.height, lc.round, _py_block_id(lc.block_id),
+                                  [CommitSig(s.block_id_flag, _take(s.validator_address, s.validator_address_len),
+                                             (s.ts_seconds, s.ts_nanos), _take(s.signature, s.signature_len))
+                                   for s in (lc.sigs[j] for j in range(lc.n_sigs))])
+        return self._commit
+
+    height = property(lambda self: self.decoded().height)
+    round = property(lambda self: self.decoded().round)
+    block_id = property(lambda self: self.decoded().block_id)
+    signatures = property(lambda self: self.decoded().signatures)
+
+    def __eq__(self, o):
+        if isinstance(o, ViewCommit):
+            o = o.decoded()
+        return self.decoded() == o if isinstance(o, Commit) else NotImplemented
+
+    def __repr__(self):
+        return "View" + repr(self.decoded())
+
+
+def _py_block(c: CBlock, raw: bytes, owner: _ViewsOwner) -> FullBlock:
+    """A FullBlock copied out of a tmv_block view; its last commit stays in the view."""
+    h = c.header
+    hdr = Header((h.chain_id or b"").decode("ascii"), h.height, (h.time_seconds, h.time_nanos),
+                 _py_block_id(h.last_block_id), *[_take(getattr(h, f).p, getattr(h, f).len) for f in _HASH_FIELDS],
+                 version_block=h.version_block, version_app=h.version_app)
+    commit = ViewCommit(c.last_commit, owner) if c.last_commit else None
+    return FullBlock(hdr, [_take(c.txs[j].p, c.txs[j].len) for j in range(c.n_txs)], [], commit, raw)
+
+
+def _py_views(L, views, w: WireWindow) -> List[Optional[FullBlock]]:
+    """The handled blocks of a views object, which the blocks' commits keep alive."""
+    owner = _ViewsOwner(L, views, w)
+    out = []
+    for i in range(w.n):
+        p = L.tmv_block_views_block(views, i)
+        out.append(_py_block(p.contents, w.raws[i], owner) if p else None)
+    return out
+
+
+def blocks_parse_wire(raws: List[bytes], lib=None) -> List[Optional[FullBlock]]:
+    """The strict scanner alone: each block decoded from its canonical
+    protobuf bytes (its `raw` the bytes themselves), None where the bytes are
+    not handled (blocks_validate_wire names the reason)."""
+    L = _setup_block_wire(lib or _native.lib())
+    w = WireWindow(raws)
+    views = ctypes.c_void_p()
+    rc = L.tmv_blocks_parse_wire(ctypes.cast(w.data, _u8p), w.off, w.n, None, ctypes.byref(views))
+    if rc < 0:
+        raise NativeError(f"tmv_blocks_parse_wire failed ({rc})")
+    return _py_views(L, views, w)
+
+
+def blocks_validate_wire(ctx, raws: List[bytes], part_size: int = 0, lib=None, decode: bool = False
+                         ) -> List[WireVerdict]:
+    """Block.ValidateBasic of each serialised block from its bytes
+    (tmv_blocks_validate_wire): a window of at least TMV_DEVICE_BLOCK_MIN
+    handled blocks is hashed on the device in one upload.  part_size != 0 adds
+    every block's part-set header; decode=True the decoded view of every
+    handled block (its last commit a ViewCommit)."""
+    L = _setup_block_wire(lib or _native.lib())
+    w = WireWindow(raws)
+    n, m = w.n, max(1, w.n)
+    results, reason = (ctypes.c_int32 * m)(), (ctypes.c_int32 * m)()
+    errs = ctypes.create_string_buffer(ERR_STRIDE * m)
+    hashes, has = (ctypes.c_uint8 * (32 * m))(), (ctypes.c_uint8 * m)()
+    totals, phash = (ctypes.c_uint32 * m)(), (ctypes.c_uint8 * (32 * m))()
+    views = ctypes.c_void_p()
+    rc = L.tmv_blocks_validate_wire(_handle(ctx), ctypes.cast(w.data, _u8p), w.off, n, part_size, results, reason,
+                                    errs, ERR_STRIDE, ctypes.cast(hashes, _u8p), ctypes.cast(has, _u8p), totals,
+                                    ctypes.cast(phash, _u8p), ctypes.byref(views) if decode else None)
+    if rc < 0:
+        raise NativeError(f"tmv_blocks_validate_wire failed ({rc})")
+    blocks = _py_views(L, views, w) if decode else [None] * n
+    raw_h, raw_p, err_raw = bytes(hashes), bytes(phash), errs.raw
+    out = []
+    for i in range(n):
+        text = None
+        if results[i] == WIRE_INVALID:
+            text = err_raw[i * ERR_STRIDE:(i + 1) * ERR_STRIDE].split(b"\0", 1)[0].decode()
+        out.append(WireVerdict(results[i], WIRE_REASONS[reason[i]], text,
+                               raw_h[32 * i:32 * i + 32] if has[i] else None,
+                               (totals[i], raw_p[32 * i:32 * i + 32]) if part_size else None, blocks[i]))
+    return out
 
 
 # ---------------------------------------------------------------- ABCI results and consensus params

@@ -3,8 +3,10 @@
 carry random hashes, every header here has the real LastCommitHash, DataHash
 and EvidenceHash of its block, its LastBlockID is the previous block's
 BlockID{Header.Hash, part-set header of `raw`}, and every commit signs that
-BlockID.  `raw` is arbitrary bytes of a chosen length (the serialised block is
-out of scope: only its part set is read).  make_stateful_chain adds a recorded
+BlockID.  `raw` is arbitrary bytes of a chosen length (only its part set is read),
+or with wire=True the block's real protobuf encoding (testing/block_wire.py),
+so that the BlockIDs and signatures bind to the part sets of real blocks
+(chains.blocksync_replay_wire).  make_stateful_chain adds a recorded
 application: the headers then carry the real AppHash, ConsensusHash and
 LastResultsHash as well (chains.blocksync_replay_stateful).  Input generation
 only; the hashes are restated with hashlib, never taken from the engine.
@@ -17,6 +19,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from .block_wire import encode_block
 from .factory import _field, _merkle, _uvarint, _valset_hash, header_hash, key_seed
 
 T0 = 1577836800
@@ -106,7 +109,7 @@ def make_stateful_chain(n_blocks: int, n_vals: int = 5, chain_id: str = "test_ch
     record holds one result per transaction (data of data_len[0]..data_len[1]
     bytes) and a random app hash, and block h + 1's header commits to both.
     Returns (ReplayState before block 1, [FullBlock], [BlockID], [BlockRecord]);
-    **kw goes to make_full_chain."""
+    **kw goes to make_full_chain (wire=True among them)."""
     from .. import chains
     ex = _Execution(seed, data_len, block_max_bytes, block_max_gas)
     vals, blocks, ids = make_full_chain(n_blocks, n_vals, chain_id, seed, _execution=ex, **kw)
@@ -121,7 +124,7 @@ def make_full_chain(n_blocks: int, n_vals: int = 5, chain_id: str = "test_chain_
                     raw_len: Sequence[int] = (1, 70000), part_size: int = 65536, txs: Sequence[int] = (0, 5),
                     tx_len: Sequence[int] = (1, 300), evidence_at: Optional[dict] = None,
                     absent: Sequence[int] = (), sign: bool = True, header_edit: Optional[dict] = None,
-                    _execution: Optional[_Execution] = None):
+                    _execution: Optional[_Execution] = None, wire: bool = False):
     """Heights 1..n_blocks (initial height 1) over a static n_vals-validator set
     of power 10.  Block h carries LastCommit = the commit for h-1 (a commit
     without signatures at height 1), txs[0]..txs[1] transactions of
@@ -132,6 +135,9 @@ def make_full_chain(n_blocks: int, n_vals: int = 5, chain_id: str = "test_chain_
     header_edit: {height: function Header -> Header} applied before the header
     is hashed, so the chain goes on from the edited header and its commit signs
     it (a block that is wrong and properly signed).
+    wire=True sets each block's `raw` to its canonical protobuf encoding
+    (block_wire.encode_block) in place of the drawn bytes; the draws themselves
+    stay the same, so the transactions and keys do not depend on the switch.
     Returns (ValidatorSet, [FullBlock], [BlockID of each block])."""
     from .. import host as H
     from ..types.canonical import BlockID, PartSetHeader
@@ -166,6 +172,8 @@ def make_full_chain(n_blocks: int, n_vals: int = 5, chain_id: str = "test_chain_
                        proposer_address=vals.validators[0].address)
         if header_edit and h in header_edit:
             hdr = header_edit[h](hdr)
+        if wire:
+            raw = encode_block(H.FullBlock(hdr, btxs, evs, last_commit))[0]
         blocks.append(H.FullBlock(hdr, btxs, evs, last_commit, raw))
         total, phash = part_set_header(raw, part_size)
         last_id = H.BlockID(header_hash(hdr), total, phash)
