@@ -555,6 +555,83 @@ int tmv_blocks_parse_wire(const uint8_t *data, const uint32_t *block_off, uint32
 const tmv_block *tmv_block_views_block(const tmv_block_views *v, uint32_t i); /* NULL for a block that was not handled */
 void tmv_block_views_free(tmv_block_views *v);
 
+/* ---- light blocks from their protobuf bytes (types/light.go) ---- */
+/* Statesync's backfill fetches one tendermint.types.LightBlock per height from
+ * peers (internal/statesync/reactor.go:437-600) and the light store keeps
+ * LightBlocks as marshalled protobuf (light/store/db/db.go); what
+ * LightBlock.ValidateBasic hashes -- Header.Hash and ValidatorSet.Hash -- sits
+ * in those bytes.  tmv_light_blocks_validate_wire validates a window of light
+ * blocks from the bytes: data[block_off[i], block_off[i+1]) is the LightBlock
+ * message of block i (n + 1 offsets, block_off[0] = 0, never decreasing).
+ *
+ * The contract is tmv_blocks_validate_wire's, extended to LightBlock
+ * {signed_header = 1, validator_set = 2}, SignedHeader{header = 1, commit = 2},
+ * ValidatorSet{validators = 1 repeated, proposer = 2, total_voting_power = 3},
+ * Validator{address = 1, pub_key = 2 (nullable = false), voting_power = 3,
+ * proposer_priority = 4} and crypto.PublicKey{ed25519 = 1 | secp256k1 = 2 |
+ * sr25519 = 3}.  The scanner (csrc/host/light_wire.h) accepts the canonical
+ * encoding only, by block_wire.h's rules with one difference: a oneof member
+ * is written even when empty, so the zero-absent rule does not apply inside
+ * PublicKey.  The message fields are pointers in the reference: absent is nil,
+ * present with length 0 is non-nil and empty, and the views keep that apart.
+ * Everything else is TMV_WIRE_NOT_HANDLED with the first problem in byte order
+ * in reason[i], and so is everything for which LightBlockFromProto
+ * (types/light.go:104-128) fails for a reason that is no ValidateBasic failure,
+ * or panics:
+ *   KEY       a PublicKey whose oneof is unset, or whose key is not 32 / 33 /
+ *             32 bytes (crypto/encoding/codec.go:49-78)
+ *   PROPOSER  validator_set present without proposer (ValidatorFromProto(nil)),
+ *             or a proposer whose message bytes equal no entry of a non-empty
+ *             `validators` (the views carry its index; an empty set has none)
+ *   POWER     the clipped running sum of the voting powers exceeds
+ *             MaxTotalVotingPower (types/validator_set.go:295-309 panics)
+ * total_voting_power is scanned and dropped, as ValidatorSetFromProto drops it.
+ *
+ * Handled blocks: results[i] and the text at errs + i*err_stride are
+ * LightBlock.ValidateBasic(chain_id) (types/light.go:37-60), byte for byte:
+ * "missing signed header", "missing validator set", "invalid signed header: "
+ * + SignedHeader.ValidateBasic, "invalid validator set: " +
+ * ValidatorSet.ValidateBasic (types/validator_set.go:82-98), "expected
+ * validator hash of header to match validator set hash (%X != %X)".
+ * hash_out + 32*i: Header.Hash(), which backfill compares with the trusted
+ * LastBlockID.Hash; has_hash[i] bit 0 set when the header has one (a header is
+ * present and its ValidatorsHash is not empty).  vals_hash_out + 32*i:
+ * ValidatorSet.Hash(); has_hash[i] bit 1 set when it was computed (the set is
+ * present and not empty).  All three may be NULL.  Commit.Hash is not part of
+ * LightBlock.ValidateBasic and is not computed.
+ *
+ * A call with at least $TMV_DEVICE_HASH_MIN handled light blocks (the light
+ * client's knob, default 32; read on every call) makes one
+ * tmv_merkle_wire_roots call over the caller's bytes (a weak reference): one
+ * upload and one tree launch for every Header.Hash and every ValidatorSet.Hash
+ * of the window, whatever the key types.  Smaller calls, calls above the
+ * engine's limits and a build without the engine hash the views on the host --
+ * a re-encoding of what the scanner decoded.
+ *
+ * views_out (may be NULL): the views, freed with tmv_light_block_views_free;
+ * they point into `data`, which must outlive them.  The two accessors go
+ * straight into a tmv_light_job; both return NULL for a block that was not
+ * handled and for a nil signed header / validator set; a nil header or commit
+ * inside the tmv_signed_header is NULL.  Returns the number of blocks that are
+ * not TMV_WIRE_OK, or < 0 (then *views_out is NULL). */
+#define TMV_WIRE_REASON_KEY 12      /* a PublicKey with no oneof member, or a key of the wrong size */
+#define TMV_WIRE_REASON_PROPOSER 13 /* a validator set without proposer, or a proposer that is none of its validators */
+#define TMV_WIRE_REASON_POWER 14    /* the total voting power exceeds MaxTotalVotingPower */
+
+typedef struct tmv_light_block_views tmv_light_block_views;
+
+int tmv_light_blocks_validate_wire(tmv_ctx *ctx, const char *chain_id, const uint8_t *data,
+                                   const uint32_t *block_off, uint32_t n, int32_t *results, int32_t *reason,
+                                   char *errs, size_t err_stride, uint8_t *hash_out, uint8_t *has_hash,
+                                   uint8_t *vals_hash_out, tmv_light_block_views **views_out /* may be NULL */);
+/* The scanner alone: reason[i] (may be NULL) and the views of n light blocks.
+ * Returns the number of blocks that were not handled, or < 0. */
+int tmv_light_blocks_parse_wire(const uint8_t *data, const uint32_t *block_off, uint32_t n, int32_t *reason,
+                                tmv_light_block_views **out);
+const tmv_signed_header *tmv_light_block_views_header(const tmv_light_block_views *v, uint32_t i);
+const tmv_validator_set *tmv_light_block_views_vals(const tmv_light_block_views *v, uint32_t i);
+void tmv_light_block_views_free(tmv_light_block_views *v);
+
 /* ---- ABCI results and consensus params (abci/types/types.go, types/params.go) ---- */
 /* Calls with at least $TMV_DEVICE_RESULTS_MIN results (default 4096; DESIGN.md
  * section 21) hash on the device in one tmv_tx_results_hashes call (a weak

@@ -302,6 +302,38 @@ int tmv_merkle_span_roots(tmv_ctx *ctx, const uint8_t *data, uint32_t data_len,
                           const tmv_leaf_span *leaves, uint32_t n_leaves,
                           const uint32_t *tree_off, uint32_t n_trees, uint8_t *root_out);
 
+/* tmv_merkle_span_roots with ValidatorSet.Hash leaves hashed from the protobuf
+ * bytes of the validators themselves: what LightBlock.ValidateBasic hashes
+ * (types/light.go:37-60: Header.Hash and ValidatorSet.Hash) for a window of
+ * serialised light blocks, in one call.
+ * A ValidatorSet.Hash leaf is SimpleValidator{pub_key = 1, voting_power = 2}
+ * (types/validator.go:154-170).  In the canonical encoding of Validator
+ * {address = 1, pub_key = 2, voting_power = 3, proposer_priority = 4} the two
+ * fields lie next to each other, 12 LL <PublicKey> [18 <varint>], and
+ * SimpleValidator's bytes are those bytes with the tags replaced, 12 -> 0a and
+ * 18 -> 10, whatever the key type.  A validator leaf names that span: pos (the
+ * 12), len (to the end of the power's varint), power_at (the 18's offset in
+ * the span, or len for a power of 0, which is not encoded).  Its hash is
+ *   SHA-256(00 || 0a || data[pos+1, pos+power_at) || 10 || data[pos+power_at+1, pos+len))
+ * without the 10 and the tail when power_at == len.  The engine substitutes
+ * bytes 0 and power_at of the span and never interprets the rest.
+ * Leaves [0, n_leaves) are tmv_merkle_span_roots leaves with its flags and
+ * rules; leaves [n_leaves, n_leaves + n_val_leaves) are the validator leaves;
+ * tree_off indexes the combined array (tree_off[n_trees] = n_leaves +
+ * n_val_leaves), so a tree may hold both kinds.  Either table may be empty.
+ * One upload (bytes, both tables and offsets), at most one k_span_leaves
+ * launch, one k_valset_span_leaves launch (one lane per validator, one SHA-256
+ * block each), one k_merkle_tree launch, one copy back.
+ * TMV_ERR_ARG: tmv_merkle_span_roots' cases, and a validator leaf with len < 2,
+ * len > 54, power_at < 2, power_at > len or pos + len > data_len, and n_leaves +
+ * n_val_leaves > 2^26; everything is checked before anything is uploaded.
+ * n_trees == 0 returns 0.  Synchronous, device 0; 0 or < 0 on error. */
+typedef struct { uint32_t pos, len, power_at; } tmv_val_span;
+int tmv_merkle_wire_roots(tmv_ctx *ctx, const uint8_t *data, uint32_t data_len,
+                          const tmv_leaf_span *leaves, uint32_t n_leaves,
+                          const tmv_val_span *val_leaves, uint32_t n_val_leaves,
+                          const uint32_t *tree_off, uint32_t n_trees, uint8_t *root_out);
+
 /* Merkle inclusion proofs (crypto/merkle/proof.go).  Blocksync's replay loop
  * builds every block's part set (internal/blocksync/reactor.go:563-582:
  * first.MakePartSet -> NewPartSetFromData, types/part_set.go:172-200 ->
@@ -417,7 +449,8 @@ int tmv_verify_mixed_batch_ex(tmv_ctx *ctx, uint32_t flags, const uint8_t *kind,
  * "k_merkle_leaves", "k_merkle_tree_levels", "k_merkle_aunts" and "k_merkle_verify_proofs" (the launches
  * of tmv_merkle_proofs / tmv_merkle_verify_proofs), "k_merkle_digests_long" and "k_merkle_value_ops"
  * (tmv_merkle_value_ops), "k_commit_leaves" (tmv_commit_hashes), "k_result_leaves" (tmv_tx_results_hashes),
- * "k_span_leaves" (tmv_merkle_span_roots) -- is bracketed by HIP timing events on the stream it runs on
+ * "k_span_leaves" (tmv_merkle_span_roots, tmv_merkle_wire_roots), "k_valset_span_leaves"
+ * (tmv_merkle_wire_roots) -- is bracketed by HIP timing events on the stream it runs on
  * (process-wide, two event records per launch); 0 turns it off.
  * tmv_kernel_timing_read waits for the recorded launches of `kernel`, returns
  * their summed duration and count, and forgets them.  No reference

@@ -65,7 +65,7 @@ EXPORTS = [
     "tmv_verify_votes", "tmv_vote_sign_bytes_device", "tmv_verify_votes_and_extensions",
     "tmv_vote_extension_sign_bytes_device", "tmv_merkle_roots",
     "tmv_merkle_aunt_offsets", "tmv_merkle_proofs", "tmv_merkle_verify_proofs", "tmv_merkle_value_ops",
-    "tmv_commit_hashes", "tmv_tx_results_hashes", "tmv_merkle_span_roots",
+    "tmv_commit_hashes", "tmv_tx_results_hashes", "tmv_merkle_span_roots", "tmv_merkle_wire_roots",
     "tmv_kernel_timing", "tmv_kernel_timing_read", "tmv_metrics_read", "tmv_metrics_reset",
     # include/tmhost.h
     "tmv_batch_new", "tmv_batch_add", "tmv_batch_len", "tmv_batch_verify", "tmv_batch_free",
@@ -75,6 +75,8 @@ EXPORTS = [
     "tmv_proof_ops_verify", "tmv_tx_proofs_validate",
     "tmv_commit_hash_many", "tmv_blocks_validate_basic",
     "tmv_blocks_validate_wire", "tmv_blocks_parse_wire", "tmv_block_views_block", "tmv_block_views_free",
+    "tmv_light_blocks_validate_wire", "tmv_light_blocks_parse_wire", "tmv_light_block_views_header",
+    "tmv_light_block_views_vals", "tmv_light_block_views_free",
     "tmv_results_hash_many", "tmv_consensus_params_hash", "tmv_block_results_verify", "tmv_consensus_params_verify",
     "tmv_vote_extension_sign_bytes", "tmv_vote_extension_template_encode", "tmv_verify_extended_votes",
 ]
@@ -217,6 +219,8 @@ def lib() -> ctypes.CDLL:
         L.tmv_tx_results_hashes.argtypes = [vp, ctypes.c_uint32, u32p, i64p, i64p, u8p, u32p, u32p, ctypes.c_uint32,
                                             u8p, u32p, u8p]
         L.tmv_merkle_span_roots.argtypes = [vp, u8p, ctypes.c_uint32, u32p, ctypes.c_uint32, u32p, ctypes.c_uint32, u8p]
+        L.tmv_merkle_wire_roots.argtypes = [vp, u8p, ctypes.c_uint32, u32p, ctypes.c_uint32, u32p, ctypes.c_uint32, u32p,
+                                            ctypes.c_uint32, u8p]
         L.tmv_merkle_verify_proofs.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, i64p, i64p, u8p, u8p, u32p, u8p,
                                                u8p, u32p, i8p, u8p, u8p, u8p]
         L.tmv_merkle_value_ops.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, u8p, u32p, u32p, u8p, u32p, i64p, i64p,
@@ -624,6 +628,39 @@ class Context:
                                                     None if spans is None else _p(spans, ctypes.c_uint32),
                                                     n_leaves or 0, _p(tree_off, ctypes.c_uint32), n_trees, _p(out)),
                     "tmv_merkle_span_roots")
+        return out[:n_trees]
+
+    def merkle_wire_roots(self, data, spans, val_spans, tree_off: np.ndarray, data_len=None, n_leaves=None,
+                          n_val_leaves=None) -> np.ndarray:
+        """Merkle roots over spans and validator spans of one buffer
+        (tmv_merkle_wire_roots): (n_trees, 32) uint8.  data and spans as for
+        merkle_span_roots; val_spans: (n, 3) uint32 rows of (pos, len,
+        power_at), or None for a null pointer; tree t holds the leaves
+        [tree_off[t], tree_off[t+1]) of spans followed by val_spans.
+        data_len / n_leaves / n_val_leaves override the arrays' sizes."""
+        n_trees = len(tree_off) - 1
+        out = np.zeros((max(n_trees, 1), 32), np.uint8)
+        tree_off = np.ascontiguousarray(tree_off, np.uint32)
+        if data is not None:
+            data = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray)) else np.ascontiguousarray(
+                data, np.uint8)
+            if data_len is None:
+                data_len = len(data)
+            data = data if data.size else np.zeros(1, np.uint8)
+
+        def table(t, n):
+            if t is None:
+                return None, n or 0
+            t = np.ascontiguousarray(t, np.uint32).reshape(-1, 3)
+            n = len(t) if n is None else n
+            return (t if t.size else np.zeros((1, 3), np.uint32)), n
+        spans, n_leaves = table(spans, n_leaves)
+        val_spans, n_val_leaves = table(val_spans, n_val_leaves)
+        self._check(self._lib.tmv_merkle_wire_roots(self._h, None if data is None else _p(data), data_len or 0,
+                                                    None if spans is None else _p(spans, ctypes.c_uint32), n_leaves,
+                                                    None if val_spans is None else _p(val_spans, ctypes.c_uint32),
+                                                    n_val_leaves, _p(tree_off, ctypes.c_uint32), n_trees, _p(out)),
+                    "tmv_merkle_wire_roots")
         return out[:n_trees]
 
     def merkle_roots(self, data, leaf_off: np.ndarray, tree_off: np.ndarray) -> np.ndarray:

@@ -139,6 +139,121 @@ def verify_sequential(ctx, trusted: LightBlock, blocks: List[LightBlock], trusti
     return done, None
 
 
+def verify_sequential_wire(ctx, trusted: LightBlock, raws: List[bytes], trusting_period_ns: int,
+                           now: Tuple[int, int], max_clock_drift_ns: int = 10 * 10**9, window: int = 1000,
+                           verify_many=None, depth: Optional[int] = None, lib=None
+                           ) -> Tuple[int, Optional[VerificationFailed]]:
+    """verify_sequential over light blocks as the light store and peers hold
+    them: `raws` holds each light block's protobuf bytes (tmproto.LightBlock,
+    heights trusted+1, ...), nothing is decoded by the caller.  Per window one
+    tmv_light_blocks_validate_wire call (H.light_blocks_validate_wire) yields
+    the views, and the light jobs take signed header and validator set by
+    pointer (H.ViewSignedHeader, H.ViewValidatorSet).  verify_many / depth as
+    for verify_sequential; lib: the library of the wire call.  Returns what
+    verify_sequential returns on the decoded blocks.  A light block whose
+    bytes the strict scanner hands back, or that has no
+    header, ends the run at its place with a LIGHT_ERR_OTHER "light block wire
+    not handled: <reason name>": the reference would decode it and go on, and
+    this model has no Go decoder to fall back to."""
+    if depth is None:
+        depth = 1 if verify_many else 2
+    if verify_many:
+        light, prepare = verify_many, (lambda jobs: jobs)
+    else:
+        fn = H._setup_light(H._setup(H._native.lib())).tmv_light_verify_many
+        light = lambda pj: H.run_light_jobs(fn, ctx.handle, pj)
+        prepare = H.PreparedLightJobs
+    chain_id = trusted.signed_header.header.chain_id
+
+    def run(w):
+        pj, stop = w
+        return light(pj), stop
+
+    # a window's views come from its own bytes, but its first job's trusted
+    # header is the window before's last block: the windows are built in order
+    # on this thread, the engine calls run on the in_order threads
+    def windows():
+        p = trusted
+        for lo in range(0, len(raws), window):
+            vs = H.light_blocks_validate_wire(ctx, chain_id, raws[lo:lo + window], lib, decode=True)
+            jobs, stop = [], None
+            for v in vs:
+                sh = v.signed_header
+                if v.result == H.WIRE_NOT_HANDLED or sh is None or not sh.ptr.contents.header:
+                    stop = "light block wire not handled: " + (v.reason if v.result == H.WIRE_NOT_HANDLED
+                                                               else "MISSING")
+                    break
+                lb = LightBlock(sh, v.vals)
+                jobs.append(LightJob(p.signed_header, None, sh, v.vals, trusting_period_ns, now, max_clock_drift_ns,
+                                     mode=H.LIGHT_ADJACENT))
+                p = lb
+            yield prepare(jobs), (jobs, stop)
+            if stop is not None:
+                return
+
+    done = 0
+    prev_height = trusted.height
+    for res, (jobs, stop) in in_order(windows(), run, depth):
+        for jb, (kind, text) in zip(jobs, res):
+            if kind != H.LIGHT_OK:
+                return done, VerificationFailed(prev_height, jb.untrusted.height, kind, text)
+            prev_height = jb.untrusted.height
+            done += 1
+        if stop is not None:
+            return done, VerificationFailed(prev_height, prev_height + 1, H.LIGHT_ERR_OTHER, stop)
+    return done, None
+
+
+def _hex_upper(b: Optional[bytes]) -> str:
+    return (b or b"").hex().upper()
+
+
+def statesync_backfill(ctx, chain_id: str, raws: List[bytes], trusted_block_id_hash: bytes, window: int = 600,
+                       start_height: Optional[int] = None, lib=None
+                       ) -> Tuple[int, Optional[Tuple[int, str]], List[int]]:
+    """Statesync's backfill (internal/statesync/reactor.go:437-600) over light
+    blocks as peers deliver them, newest height first: `raws` holds the
+    tmproto.LightBlock bytes of heights start_height, start_height - 1, ...
+    (start_height: default the first block's own height), and
+    trusted_block_id_hash is the trusted BlockID's hash for the first of them.
+    One tmv_light_blocks_validate_wire call per window; then per block, in the
+    reference's order: LightBlock.ValidateBasic(chain_id) and the height
+    (reactor.go:511-523, "received invalid light block: ..."), Header.Hash
+    against the running trusted hash (reactor.go:550-560, "received invalid
+    light block. Expected hash %v, got: %v"), then trusted =
+    header.LastBlockID.Hash.  There is no signature check in this loop.
+    Returns (light blocks accepted, None or (height, text) of the first
+    failure, the heights at which ValidatorsHash != NextValidatorsHash,
+    reactor.go:569-577: counted from the second accepted block on, as the
+    reference's lastValidatorSet is nil for the first).  The reference retries
+    a failed height with another peer; this model stops there.  A light block
+    that the strict scanner hands back ends it with
+    "light block wire not handled: <reason name>"."""
+    trusted = trusted_block_id_hash
+    done, changes = 0, []
+    height = start_height
+    for lo in range(0, len(raws), window):
+        for v in H.light_blocks_validate_wire(ctx, chain_id, raws[lo:lo + window], lib, decode=True):
+            if v.result == H.WIRE_NOT_HANDLED:
+                return done, (height if height is not None else 0, "light block wire not handled: " + v.reason), changes
+            got = v.signed_header.height if v.result == H.WIRE_OK else None
+            if height is None and got is not None:
+                height = got
+            if v.result != H.WIRE_OK or got != height:
+                err = v.error if v.result != H.WIRE_OK else "%!w(<nil>)"  # fmt.Errorf("...%w", nil)
+                return done, (height if height is not None else 0, "received invalid light block: " + err), changes
+            if trusted != v.hash:
+                return done, (height, "received invalid light block. Expected hash %s, got: %s"
+                              % (_hex_upper(trusted), _hex_upper(v.hash))), changes
+            hdr = v.signed_header.header
+            if done > 0 and hdr.validators_hash != hdr.next_validators_hash:
+                changes.append(height)
+            trusted = hdr.last_block_id.hash
+            done += 1
+            height -= 1
+    return done, None, changes
+
+
 def schedule(last_verified: int, last_failed: int) -> int:
     """Client.schedule (light/client.go:721-725)."""
     return last_verified + (last_failed - last_verified) * SKIPPING_NUM // SKIPPING_DEN

@@ -19,4 +19,9 @@ hipError_t launch_span_roots(const uint8_t *data, const tmv_leaf_span *leaves, u
                              const uint32_t *tree_off, uint32_t n_trees, uint32_t max_leaves, uint32_t *node_a,
                              uint32_t *node_b, uint8_t *out, hipStream_t stream);
 
+// k_span_leaves alone: the leaf hashes of launch_span_roots into node (no
+// launch for n_leaves == 0).
+hipError_t launch_span_leaves(const uint8_t *data, const tmv_leaf_span *leaves, uint32_t n_leaves, uint32_t *node,
+                              hipStream_t stream);
+
 }  // namespace tmv

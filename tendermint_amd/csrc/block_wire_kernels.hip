@@ -106,17 +106,21 @@ k_span_leaves(const uint8_t *__restrict__ data, const tmv_leaf_span *__restrict_
   o[1] = make_uint4(st[4], st[5], st[6], st[7]);
 }
 
+hipError_t launch_span_leaves(const uint8_t *data, const tmv_leaf_span *leaves, uint32_t n_leaves, uint32_t *node,
+                              hipStream_t stream) {
+  if (!n_leaves) return hipSuccess;
+  void *tok = ktimer::begin(ktimer::kSpanLeaves, stream);
+  hipLaunchKernelGGL(k_span_leaves, dim3((n_leaves + kSpanBlock - 1) / kSpanBlock), dim3(kSpanBlock), 0, stream,
+                     data, leaves, n_leaves, node);
+  ktimer::end(tok, stream);
+  return hipGetLastError();
+}
+
 hipError_t launch_span_roots(const uint8_t *data, const tmv_leaf_span *leaves, uint32_t n_leaves,
                              const uint32_t *tree_off, uint32_t n_trees, uint32_t max_leaves, uint32_t *node_a,
                              uint32_t *node_b, uint8_t *out, hipStream_t stream) {
-  if (n_leaves) {
-    void *tok = ktimer::begin(ktimer::kSpanLeaves, stream);
-    hipLaunchKernelGGL(k_span_leaves, dim3((n_leaves + kSpanBlock - 1) / kSpanBlock), dim3(kSpanBlock), 0, stream,
-                       data, leaves, n_leaves, node_a);
-    ktimer::end(tok, stream);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
+  const hipError_t e = launch_span_leaves(data, leaves, n_leaves, node_a, stream);
+  if (e != hipSuccess) return e;
   return launch_merkle_tree(tree_off, n_trees, max_leaves, node_a, node_b, out, stream);
 }
 

@@ -8,6 +8,26 @@
 #pragma once
 #include "block_wire_hash.h"
 
+namespace {
+
+// The rules of a tmv_leaf_span table over data_len bytes (tmv_merkle_span_roots,
+// and the span leaves of tmv_merkle_wire_roots): 0, or TMV_ERR_ARG with "<w>: ...".
+int span_leaves_rc(const std::string &w, const tmv_leaf_span *leaves, uint32_t n_leaves, uint32_t data_len) {
+  for (uint32_t i = 0; i < n_leaves; i++) {
+    const tmv_leaf_span &s = leaves[i];
+    if (s.flags & ~(0xffu | TMV_SPAN_TAG | TMV_SPAN_PREHASH)) { set_error(w + ": unknown flag"); return TMV_ERR_ARG; }
+    if ((s.flags & TMV_SPAN_TAG) && (s.flags & TMV_SPAN_PREHASH)) {
+      set_error(w + ": TAG together with PREHASH");
+      return TMV_ERR_ARG;
+    }
+    if (!(s.flags & TMV_SPAN_TAG) && (s.flags & 0xffu)) { set_error(w + ": tag byte without TAG"); return TMV_ERR_ARG; }
+    if ((uint64_t)s.pos + s.len > data_len) { set_error(w + ": span outside the data"); return TMV_ERR_ARG; }
+  }
+  return 0;
+}
+
+}  // namespace
+
 extern "C" {
 
 int tmv_merkle_span_roots(tmv_ctx *ctx, const uint8_t *data, uint32_t data_len, const tmv_leaf_span *leaves,
@@ -28,16 +48,7 @@ int tmv_merkle_span_roots(tmv_ctx *ctx, const uint8_t *data, uint32_t data_len, 
   uint32_t max_leaves = 0;
   if ((rc = offsets_rc(who, "tree_off", tree_off, n_trees, &max_leaves)) != 0) return rc;
   if (tree_off[n_trees] != n_leaves) { set_error(w + ": tree_off does not end at n_leaves"); return TMV_ERR_ARG; }
-  for (uint32_t i = 0; i < n_leaves; i++) {
-    const tmv_leaf_span &s = leaves[i];
-    if (s.flags & ~(0xffu | TMV_SPAN_TAG | TMV_SPAN_PREHASH)) { set_error(w + ": unknown flag"); return TMV_ERR_ARG; }
-    if ((s.flags & TMV_SPAN_TAG) && (s.flags & TMV_SPAN_PREHASH)) {
-      set_error(w + ": TAG together with PREHASH");
-      return TMV_ERR_ARG;
-    }
-    if (!(s.flags & TMV_SPAN_TAG) && (s.flags & 0xffu)) { set_error(w + ": tag byte without TAG"); return TMV_ERR_ARG; }
-    if ((uint64_t)s.pos + s.len > data_len) { set_error(w + ": span outside the data"); return TMV_ERR_ARG; }
-  }
+  if ((rc = span_leaves_rc(w, leaves, n_leaves, data_len)) != 0) return rc;
   if ((rc = c.open()) != 0) return rc;
   tmh::StageLayout L;
   // the data first (16-byte aligned for the kernel's dword loads), 3 spare

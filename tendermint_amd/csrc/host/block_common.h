@@ -80,7 +80,7 @@ inline tmh::Header header_of(const tmv_header &h) {
   return o;
 }
 
-inline tmh::Error commit_validate_basic(const tmv_commit &c) {  // the parts Commit.ValidateBasic reads
+inline tmh::Commit commit_basic_of(const tmv_commit &c) {  // the parts Commit.ValidateBasic reads
   tmh::Commit o;
   o.height = c.height;
   o.round = c.round;
@@ -94,8 +94,10 @@ inline tmh::Error commit_validate_basic(const tmv_commit &c) {  // the parts Com
     d.timestamp = tmh::Timestamp{s.ts_seconds, s.ts_nanos};
     d.signature = tmh::ByteView(s.signature, s.signature_len);
   }
-  return tmh::CommitValidateBasic(o);
+  return o;
 }
+
+inline tmh::Error commit_validate_basic(const tmv_commit &c) { return tmh::CommitValidateBasic(commit_basic_of(c)); }
 
 // Block.ValidateBasic in front of the hashes (types/block.go:53-75): the text,
 // empty when the block comes as far as its hashes.  *h: the converted header.

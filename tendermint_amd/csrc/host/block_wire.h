@@ -65,6 +65,10 @@ enum Reason : int32_t {
   kEvidence = TMV_WIRE_REASON_EVIDENCE,
   kChainID = TMV_WIRE_REASON_CHAIN_ID,
   kLimit = TMV_WIRE_REASON_LIMIT,
+  // light blocks (light_wire.h)
+  kKey = TMV_WIRE_REASON_KEY,
+  kProposer = TMV_WIRE_REASON_PROPOSER,
+  kPower = TMV_WIRE_REASON_POWER,
 };
 
 constexpr uint32_t kHeaderLeaves = 14;

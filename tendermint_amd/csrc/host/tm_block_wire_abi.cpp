@@ -44,8 +44,8 @@ tmv_block_views *handle_of(Views *v) { return reinterpret_cast<tmv_block_views *
 using namespace tmh_block;
 using tmh_internal::parallel_for;
 
-constexpr uint64_t kEngineMaxItems = 1ull << 26;  // leaves / trees per engine call
-constexpr uint64_t kEngineMaxBytes = 1ull << 30;  // bytes per engine call
+using tmh_internal::kEngineMaxBytes;
+using tmh_internal::kEngineMaxItems;
 
 // Inside a device call, a block holding a transaction of more bytes than this
 // has its Data.Hash computed on the host: k_span_leaves hashes one leaf on one
@@ -53,8 +53,7 @@ constexpr uint64_t kEngineMaxBytes = 1ull << 30;  // bytes per engine call
 // tmv_results_hash_many's for the same kernel shape.
 // TMV_DEVICE_WIRE_MAX_TX overrides (read on every call).
 uint32_t device_wire_max_tx() {
-  const char *e = std::getenv("TMV_DEVICE_WIRE_MAX_TX");
-  return e ? (uint32_t)std::strtoul(e, nullptr, 10) : 1024u;
+  return tmh_internal::env_threshold("TMV_DEVICE_WIRE_MAX_TX", 1024u);
 }
 
 // 0 and *out, or TMV_ERR_ARG.  *not_handled: how many blocks were handed back.

@@ -64,6 +64,18 @@ struct Converted {
 int verify_commits(tmv_ctx *ctx, const tmv_commit_job *jobs, uint32_t n_jobs, int32_t *results, char *errs,
                    size_t err_stride, uint8_t *not_enough, const Converted *conv = nullptr);
 
+// What one synchronous engine call of the hashing entry points takes
+// (include/tmverify.h); larger windows stay on the host path.
+constexpr uint64_t kEngineMaxItems = 1ull << 26;  // leaves / trees per engine call
+constexpr uint64_t kEngineMaxBytes = 1ull << 30;  // bytes per engine call
+
+// A host / device threshold knob read from the environment on every call
+// (tests change it between calls): $name as an unsigned number, else dflt.
+inline uint32_t env_threshold(const char *name, uint32_t dflt) {
+  const char *e = std::getenv(name);
+  return e ? (uint32_t)std::strtoul(e, nullptr, 10) : dflt;
+}
+
 // Run fn(i) for i in [0, n) on the host worker pool (serial when small).
 template <class F>
 void parallel_for(size_t n, size_t min_per_thread, F fn) {

@@ -399,6 +399,42 @@ inline Error SignedHeaderValidateBasic(const SignedHeader &sh, const std::string
   return std::nullopt;
 }
 
+// types/validator.go:74-91.  A key without bytes stands for the nil PubKey.
+inline Error ValidatorValidateBasic(const Validator *v) {
+  if (!v) return std::string("nil validator");
+  if (v->pub_key.bytes.empty()) return std::string("validator does not have a public key");
+  if (v->voting_power < 0) return std::string("validator has negative voting power");
+  if (v->address.size() != kAddressSize)  // %v of a HexBytes: %X (libs/bytes/bytes.go:64-71)
+    return "validator address is the wrong size: " + HexUpper(v->address);
+  return std::nullopt;
+}
+
+// types/validator_set.go:82-98; vs.proposer is the index of vals.Proposer (< 0: nil)
+inline Error ValidatorSetValidateBasic(const ValidatorSet *vs) {
+  if (!vs || vs->validators.empty()) return std::string("validator set is nil or empty");
+  for (size_t i = 0; i < vs->validators.size(); i++)
+    if (Error e = ValidatorValidateBasic(&vs->validators[i])) return "invalid validator #" + std::to_string(i) + ": " + *e;
+  const bool has = vs->proposer >= 0 && (size_t)vs->proposer < vs->validators.size();
+  if (Error e = ValidatorValidateBasic(has ? &vs->validators[(size_t)vs->proposer] : nullptr))
+    return "proposer failed validate basic, error: " + *e;
+  return std::nullopt;
+}
+
+// LightBlock.ValidateBasic (types/light.go:37-60).  sh / vs: nullptr = nil;
+// header_hash = Header.Hash() (empty = nil), vals_hash = ValidatorSet.Hash(),
+// read only where the reference computes it.
+inline Error LightBlockValidateBasic(const SignedHeader *sh, const ValidatorSet *vs, const std::string &chain_id,
+                                     const Bytes &header_hash, const Bytes &vals_hash) {
+  if (!sh) return std::string("missing signed header");
+  if (!vs) return std::string("missing validator set");
+  if (Error e = SignedHeaderValidateBasic(*sh, chain_id, header_hash)) return "invalid signed header: " + *e;
+  if (Error e = ValidatorSetValidateBasic(vs)) return "invalid validator set: " + *e;
+  if (!(sh->header->validators_hash == ByteView(vals_hash)))
+    return "expected validator hash of header to match validator set hash (" + HexUpper(sh->header->validators_hash) +
+           " != " + HexUpper(vals_hash) + ")";
+  return std::nullopt;
+}
+
 // ---------------------------------------------------------------- light/verifier.go
 enum LightKind : int {
   kLightOk = 0,

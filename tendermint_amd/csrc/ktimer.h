@@ -15,8 +15,8 @@ enum Kernel : int {
   kMerkleLeavesLong = 5, kMerkleTreeLevels = 6, kMerkleAunts = 7, kMerkleVerify = 8, kMerkleLeaves = 9,
   kCommitLeaves = 10, kVoteExtSignbytes = 11, kSecpKeyTable = 12, kSecpPrepCached = 13, kSecpVerifyComb = 14,
   kMerkleDigestsLong = 15, kMerkleValueOps = 16, kResultLeaves = 17,
-  kSpanLeaves = 18,
-  kCount = 19
+  kSpanLeaves = 18, kValsetSpanLeaves = 19,
+  kCount = 20
 };
 
 void set(bool on);

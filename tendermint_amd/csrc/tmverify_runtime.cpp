@@ -1624,6 +1624,7 @@ int tmv_kernel_timing_read(tmv_ctx *ctx, const char *kernel, double *total_ms, u
   else if (!strcmp(kernel, "k_merkle_value_ops")) k = tmv::ktimer::kMerkleValueOps;
   else if (!strcmp(kernel, "k_result_leaves")) k = tmv::ktimer::kResultLeaves;
   else if (!strcmp(kernel, "k_span_leaves")) k = tmv::ktimer::kSpanLeaves;
+  else if (!strcmp(kernel, "k_valset_span_leaves")) k = tmv::ktimer::kValsetSpanLeaves;
   else { set_error("unknown timed kernel"); return TMV_ERR_ARG; }
   *total_ms = 0;
   *launches = 0;
@@ -3105,3 +3106,5 @@ int tmv_ed25519_verify_batch_device(tmv_ctx *ctx, int device, const uint8_t *d_p
 
 // tmv_merkle_span_roots
 #include "block_wire_runtime.h"
+// tmv_merkle_wire_roots
+#include "light_wire_runtime.h"

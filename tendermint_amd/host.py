@@ -587,6 +587,9 @@ class PreparedLightJobs:
         def signed(sh):
             if sh is None:
                 return None
+            if isinstance(sh, ViewSignedHeader):  # already a tmv_signed_header, inside a views object
+                k.refs.append(sh)
+                return sh.ptr
             if id(sh) not in shcache:
                 s = CSignedHeader(header(sh.header), commit(sh.commit))
                 k.refs.append(s)
@@ -596,6 +599,9 @@ class PreparedLightJobs:
         def vset(vs):
             if vs is None:
                 return None
+            if isinstance(vs, ViewValidatorSet):
+                k.refs.append(vs)
+                return vs.ptr
             if id(vs) not in vcache:
                 s = CValidatorSet(_c_validators(k, vs), len(vs.validators), vs.proposer_index)
                 k.refs.append(s)
@@ -1307,11 +1313,12 @@ class _ViewsOwner:
     """A tmv_block_views object and the bytes it points into, freed with the
     last Python object that refers to them."""
 
-    def __init__(self, L, handle, window: WireWindow):
+    def __init__(self, L, handle, window: WireWindow, free=None):
         self.L, self.handle, self.window = L, handle, window
+        self.free = free or L.tmv_block_views_free
 
     def __del__(self):
-        self.L.tmv_block_views_free(self.handle)
+        self.free(self.handle)
 
 
 class ViewCommit:
@@ -1410,6 +1417,181 @@ def blocks_validate_wire(ctx, raws: List[bytes], part_size: int = 0, lib=None, d
         out.append(WireVerdict(results[i], WIRE_REASONS[reason[i]], text,
                                raw_h[32 * i:32 * i + 32] if has[i] else None,
                                (totals[i], raw_p[32 * i:32 * i + 32]) if part_size else None, blocks[i]))
+    return out
+
+
+# ---------------------------------------------------------------- light blocks from their protobuf bytes
+# tmv_light_blocks_validate_wire / tmv_light_blocks_parse_wire (include/tmhost.h).
+
+LIGHT_WIRE_REASONS = WIRE_REASONS + ("KEY", "PROPOSER", "POWER")
+
+
+def _py_header(h: CHeader) -> Header:
+    return Header((h.chain_id or b"").decode("ascii"), h.height, (h.time_seconds, h.time_nanos),
+                  _py_block_id(h.last_block_id), *[_take(getattr(h, f).p, getattr(h, f).len) for f in _HASH_FIELDS],
+                  version_block=h.version_block, version_app=h.version_app)
+
+
+class ViewSignedHeader:
+    """The signed header of a light block decoded by
+    tmv_light_blocks_validate_wire, left where it is: a tmv_signed_header
+    inside a tmv_light_block_views object.  PreparedLightJobs passes it to
+    tmv_light_verify_many by pointer; read as a SignedHeader (header, commit,
+    height, ==) it is decoded on first use.  A nil header or commit is None."""
+
+    def __init__(self, ptr, owner: _ViewsOwner):
+        self.ptr, self.owner, self._header, self._commit = ptr, owner, None, None
+
+    @property
+    def header(self) -> Optional[Header]:
+        c = self.ptr.contents
+        if self._header is None and c.header:
+            self._header = _py_header(c.header.contents)
+        return self._header
+
+    @property
+    def commit(self) -> Optional[Commit]:
+        c = self.ptr.contents
+        if self._commit is None and c.commit:
+            self._commit = ViewCommit(c.commit, self.owner).decoded()
+        return self._commit
+
+    @property
+    def height(self) -> int:
+        return self.ptr.contents.header.contents.height
+
+    def decoded(self) -> SignedHeader:
+        return SignedHeader(self.header, self.commit)
+
+    def __eq__(self, o):
+        if isinstance(o, ViewSignedHeader):
+            o = o.decoded()
+        return self.decoded() == o if isinstance(o, SignedHeader) else NotImplemented
+
+    def __repr__(self):
+        return "View" + repr(self.decoded())
+
+
+class ViewValidatorSet:
+    """The validator set of a light block decoded by
+    tmv_light_blocks_validate_wire: a tmv_validator_set inside the views
+    object, passed to tmv_light_verify_many by pointer; read as a ValidatorSet
+    (validators, proposer_index, ==) it is decoded on first use."""
+
+    def __init__(self, ptr, owner: _ViewsOwner):
+        self.ptr, self.owner, self._vals = ptr, owner, None
+
+    def decoded(self) -> ValidatorSet:
+        if self._vals is None:
+            c = self.ptr.contents
+            self._vals = ValidatorSet([Validator(_take(v.address, v.address_len), _take(v.pub_key, v.pub_key_len),
+                                                 v.voting_power, v.key_kind, v.proposer_priority)
+                                       for v in (c.vals[j] for j in range(c.n_vals))], c.proposer_index)
+        return self._vals
+
+    validators = property(lambda self: self.decoded().validators)
+    proposer_index = property(lambda self: self.decoded().proposer_index)
+
+    def total_voting_power(self) -> int:
+        return self.decoded().total_voting_power()
+
+    def __eq__(self, o):
+        if isinstance(o, ViewValidatorSet):
+            o = o.decoded()
+        return self.decoded() == o if isinstance(o, ValidatorSet) else NotImplemented
+
+    def __repr__(self):
+        return "View" + repr(self.decoded())
+
+
+@dataclass
+class LightWireVerdict:
+    """One light block of tmv_light_blocks_validate_wire.  result: WIRE_OK /
+    WIRE_INVALID (error: LightBlock.ValidateBasic's text) / WIRE_NOT_HANDLED
+    (reason: a name of LIGHT_WIRE_REASONS).  hash: Header.Hash (None where the
+    header is nil or has none); vals_hash: ValidatorSet.Hash (None for a nil or
+    empty set); signed_header / vals: the views of a handled block, when asked
+    for (None where the block has none)."""
+    result: int
+    reason: str = "NONE"
+    error: Optional[str] = None
+    hash: Optional[bytes] = None
+    vals_hash: Optional[bytes] = None
+    signed_header: Optional[ViewSignedHeader] = None
+    vals: Optional[ViewValidatorSet] = None
+
+
+def _setup_light_wire(L):
+    if not getattr(L, "_tmhost_light_wire", False):
+        u32p, i32p = ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int32)
+        L.tmv_light_blocks_validate_wire.argtypes = [ctypes.c_void_p, ctypes.c_char_p, _u8p, u32p, ctypes.c_uint32,
+                                                     i32p, i32p, ctypes.c_char_p, ctypes.c_size_t, _u8p, _u8p, _u8p,
+                                                     ctypes.POINTER(ctypes.c_void_p)]
+        L.tmv_light_blocks_parse_wire.argtypes = [_u8p, u32p, ctypes.c_uint32, i32p, ctypes.POINTER(ctypes.c_void_p)]
+        L.tmv_light_block_views_header.restype = ctypes.POINTER(CSignedHeader)
+        L.tmv_light_block_views_header.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
+        L.tmv_light_block_views_vals.restype = ctypes.POINTER(CValidatorSet)
+        L.tmv_light_block_views_vals.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
+        L.tmv_light_block_views_free.restype = None
+        L.tmv_light_block_views_free.argtypes = [ctypes.c_void_p]
+        L._tmhost_light_wire = True
+    return L
+
+
+def _py_light_views(L, views, w: WireWindow):
+    """(signed header view, validator set view) of every light block of a views object."""
+    owner = _ViewsOwner(L, views, w, L.tmv_light_block_views_free)
+    out = []
+    for i in range(w.n):
+        sh, vs = L.tmv_light_block_views_header(views, i), L.tmv_light_block_views_vals(views, i)
+        out.append((ViewSignedHeader(sh, owner) if sh else None, ViewValidatorSet(vs, owner) if vs else None))
+    return out
+
+
+def light_blocks_parse_wire(raws: List[bytes], lib=None):
+    """The strict scanner alone: per light block (reason name, signed header
+    view, validator set view), the views None where the bytes are not handled
+    or the block has none."""
+    L = _setup_light_wire(lib or _native.lib())
+    w = WireWindow(raws)
+    reason = (ctypes.c_int32 * max(1, w.n))()
+    views = ctypes.c_void_p()
+    rc = L.tmv_light_blocks_parse_wire(ctypes.cast(w.data, _u8p), w.off, w.n, reason, ctypes.byref(views))
+    if rc < 0:
+        raise NativeError(f"tmv_light_blocks_parse_wire failed ({rc})")
+    return [(LIGHT_WIRE_REASONS[reason[i]],) + v for i, v in enumerate(_py_light_views(L, views, w))]
+
+
+def light_blocks_validate_wire(ctx, chain_id: str, raws: List[bytes], lib=None, decode: bool = False
+                               ) -> List[LightWireVerdict]:
+    """LightBlock.ValidateBasic(chain_id) of each serialised light block from
+    its bytes (tmv_light_blocks_validate_wire), with Header.Hash and
+    ValidatorSet.Hash: a window of at least TMV_DEVICE_HASH_MIN handled light
+    blocks is hashed on the device in one upload.  decode=True adds the views
+    of every handled block, which go into a LightJob as they are."""
+    L = _setup_light_wire(lib or _native.lib())
+    w = WireWindow(raws)
+    n, m = w.n, max(1, w.n)
+    results, reason = (ctypes.c_int32 * m)(), (ctypes.c_int32 * m)()
+    errs = ctypes.create_string_buffer(ERR_STRIDE * m)
+    hashes, vhashes, has = (ctypes.c_uint8 * (32 * m))(), (ctypes.c_uint8 * (32 * m))(), (ctypes.c_uint8 * m)()
+    views = ctypes.c_void_p()
+    rc = L.tmv_light_blocks_validate_wire(_handle(ctx), chain_id.encode(), ctypes.cast(w.data, _u8p), w.off, n,
+                                          results, reason, errs, ERR_STRIDE, ctypes.cast(hashes, _u8p),
+                                          ctypes.cast(has, _u8p), ctypes.cast(vhashes, _u8p),
+                                          ctypes.byref(views) if decode else None)
+    if rc < 0:
+        raise NativeError(f"tmv_light_blocks_validate_wire failed ({rc})")
+    vs = _py_light_views(L, views, w) if decode else [(None, None)] * n
+    raw_h, raw_v, err_raw = bytes(hashes), bytes(vhashes), errs.raw
+    out = []
+    for i in range(n):
+        text = None
+        if results[i] == WIRE_INVALID:
+            text = err_raw[i * ERR_STRIDE:(i + 1) * ERR_STRIDE].split(b"\0", 1)[0].decode()
+        out.append(LightWireVerdict(results[i], LIGHT_WIRE_REASONS[reason[i]], text,
+                                    raw_h[32 * i:32 * i + 32] if has[i] & 1 else None,
+                                    raw_v[32 * i:32 * i + 32] if has[i] & 2 else None, vs[i][0], vs[i][1]))
     return out
 
 
