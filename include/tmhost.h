@@ -700,6 +700,59 @@ typedef struct {
 int tmv_consensus_params_verify(tmv_ctx *ctx, const tmv_consensus_params_in *items, uint32_t n, int32_t *results,
                                 char *errs, size_t err_stride);
 
+/* ---- validator-set updates (types/validator_set.go:70-234, 362-650) ---- */
+/* What State.Update (internal/state/execution.go:527-595) does to
+ * NextValidators once per block, on the host and on one thread (DESIGN.md
+ * section 24): no engine, no context.  The calls return TMV_VALSET_OK,
+ * TMV_VALSET_ERROR (the reference returns an error; its text in err),
+ * TMV_VALSET_PANIC (the reference panics; the panic's text in err) or
+ * TMV_ERR_ARG.  On anything but TMV_VALSET_OK the outputs are not written. */
+#define TMV_VALSET_OK 0
+#define TMV_VALSET_ERROR 1
+#define TMV_VALSET_PANIC 2
+
+/* One abci.ValidatorUpdate: the key and the new power (0 removes). */
+typedef struct {
+  uint8_t key_kind;
+  const uint8_t *pub_key;
+  uint32_t pub_key_len;
+  int64_t power;
+} tmv_validator_update;
+
+/* ValidatorSet.UpdateWithChangeSet (allow_deletes != 0) of the set vals[0,
+ * n_vals) with `changes`.  The address of a change is derived from its key as
+ * NewValidator does (SHA-256 truncated to 20 bytes for ed25519 and sr25519,
+ * RIPEMD160(SHA256(key)) for secp256k1) into addr_scratch + 20 * i
+ * (20 * n_changes bytes, the caller's).  out[0, *n_out) is the new set in set
+ * order (power descending, address ascending), out_cap >= n_vals + n_changes.
+ * Its entries borrow their pointers: key and address of `vals` for a
+ * validator that stays, the key of `changes` and the address in addr_scratch
+ * for one that was added or changed; all three must outlive `out`. */
+int tmv_validator_set_update(const tmv_validator *vals, uint32_t n_vals, const tmv_validator_update *changes,
+                             uint32_t n_changes, int allow_deletes, uint8_t *addr_scratch, tmv_validator *out,
+                             uint32_t out_cap, uint32_t *n_out, char *err, size_t err_cap);
+
+/* NewValidatorSet(vals): the change set over an empty set with removals
+ * refused, then one IncrementProposerPriority(1) when the set is not empty;
+ * *proposer_index is that election's winner (-1 for an empty set).  The
+ * reference panics where the change set fails ("cannot create validator set:
+ * ...").  Pointers as tmv_validator_set_update, out_cap >= n_vals. */
+int tmv_validator_set_new(const tmv_validator_update *vals, uint32_t n_vals, uint8_t *addr_scratch, tmv_validator *out,
+                          uint32_t out_cap, uint32_t *n_out, int32_t *proposer_index, char *err, size_t err_cap);
+
+/* `steps` successive IncrementProposerPriority(times) calls on the set, as
+ * State.Update makes one per block with times = 1: the priorities of vals are
+ * updated in place and proposer_out[s] is the proposer's index after call s.
+ * One call with times = k differs from k calls with times = 1: the reference
+ * rescales and centres the priorities once per call. */
+int tmv_validator_set_rotate(tmv_validator *vals, uint32_t n_vals, int32_t times, uint32_t steps,
+                             int32_t *proposer_out, char *err, size_t err_cap);
+
+/* ValidatorSet.Hash of one set on the host: for the sets that hold secp256k1
+ * keys, which tmv_validator_set_hashes (tmverify.h) does not take.  0 or
+ * TMV_ERR_ARG. */
+int tmv_validator_set_hash_host(const tmv_validator *vals, uint32_t n_vals, uint8_t out[32]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -68,6 +68,7 @@ EXPORTS = [
     "tmv_commit_hashes", "tmv_tx_results_hashes", "tmv_merkle_span_roots", "tmv_merkle_wire_roots",
     "tmv_kernel_timing", "tmv_kernel_timing_read", "tmv_metrics_read", "tmv_metrics_reset",
     # include/tmhost.h
+    "tmv_validator_set_update", "tmv_validator_set_new", "tmv_validator_set_rotate", "tmv_validator_set_hash_host",
     "tmv_batch_new", "tmv_batch_add", "tmv_batch_len", "tmv_batch_verify", "tmv_batch_free",
     "tmv_vote_sign_bytes", "tmv_vote_template_encode", "tmv_verify_commit", "tmv_verify_commits",
     "tmv_header_hashes", "tmv_light_verify_many", "tmv_light_verify", "tmv_verify_vote_batch",

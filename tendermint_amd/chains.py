@@ -23,7 +23,7 @@ detector) is out of scope (networking).
 """
 from __future__ import annotations
 
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import Callable, Dict, List, Optional, Tuple
 
 from . import host as H
@@ -490,20 +490,24 @@ def _replay_validated(ctx, chain_id, vals, blocks, last_block_id, initial_height
     """The replay loop of blocksync_replay_full; with `stateful` (a
     _StatefulChecks) also validateBlock's state-dependent checks, each at its
     place in the reference's order; with `wire`, `blocks` holds the blocks'
-    protobuf bytes (blocksync_replay_wire)."""
+    protobuf bytes (blocksync_replay_wire).  A stateful that is a
+    _DynamicChecks supplies the validator sets and their hashes block by block
+    (blocksync_replay_dynamic); `vals` and `vals_hash` are then unused."""
+    dynamic = stateful if isinstance(stateful, _DynamicChecks) else None
+    n_apply = len(blocks) - 1 if dynamic is None else min(len(blocks) - 1, dynamic.limit)
     for b in blocks[:-1]:
         if not wire and b.raw is None:
             raise ValueError("%s: block %d has no raw bytes" % (who, b.height))
     if depth is None:
         depth = 1 if verify_commits else 2
-    if vals_hash is None:
+    if vals_hash is None and dynamic is None:
         vals_hash = validator_set_hashes(ctx, [vals])[0]
     check = verify_commits or (lambda jobs: H.verify_commits(ctx, jobs))
 
     def run(lo):
         # the previous block rides along: its BlockID is state.LastBlockID of the window's first block
         first_of = max(lo - 1, 0)
-        end = min(lo + window, len(blocks) - 1)
+        end = min(lo + window, n_apply)
         if wire:  # the window's last pair needs its second block decoded as well
             decoded, basic, psh = _wire_window(ctx, lib, blocks[first_of:end + 1], part_size,
                                                last_block_height if first_of == 0 else None)
@@ -528,8 +532,11 @@ def _replay_validated(ctx, chain_id, vals, blocks, last_block_id, initial_height
             state_height = last_block_height if prev is None else prev[0] if isinstance(prev, tuple) else prev.height
             hd = first.header
             err = basic[i][0]
+            # state.LastValidators, state.Validators and the two hashes a header must carry
+            last_vals, cur_vals, cur_hash, next_hash = (dynamic.sets(g, before) if dynamic else
+                                                        (vals, vals, vals_hash, vals_hash))
             if err is None and stateful:
-                err = stateful.version(hd)
+                err = stateful.version(hd, g)
             if err is None and hd.chain_id != chain_id:
                 err = "wrong Block.Header.ChainID. Expected %s, got %s" % (chain_id, hd.chain_id)
             if err is None and state_height == 0 and hd.height != initial_height:
@@ -541,14 +548,14 @@ def _replay_validated(ctx, chain_id, vals, blocks, last_block_id, initial_height
                                                                               _block_id_string(hd.last_block_id))
             if err is None and stateful:
                 err = stateful.app_info(hd, g, before)
-            if err is None and hd.validators_hash != vals_hash:
-                err = "wrong Block.Header.ValidatorsHash.  Expected %s, got %s" % (vals_hash.hex().upper(),
+            if err is None and hd.validators_hash != cur_hash:
+                err = "wrong Block.Header.ValidatorsHash.  Expected %s, got %s" % (cur_hash.hex().upper(),
                                                                                  hd.validators_hash.hex().upper())
-            if err is None and hd.next_validators_hash != vals_hash:
+            if err is None and hd.next_validators_hash != next_hash:
                 err = "wrong Block.Header.NextValidatorsHash.  Expected %s, got %s" % (
-                    vals_hash.hex().upper(), hd.next_validators_hash.hex().upper())
+                    next_hash.hex().upper(), hd.next_validators_hash.hex().upper())
             light = len(jobs)
-            jobs.append(H.CommitJob(H.MODE_LIGHT, chain_id, vals, ids[i], hd.height, second.last_commit))
+            jobs.append(H.CommitJob(H.MODE_LIGHT, chain_id, cur_vals, ids[i], hd.height, second.last_commit))
             full = None
             if err is None:
                 if hd.height == initial_height:
@@ -556,10 +563,12 @@ def _replay_validated(ctx, chain_id, vals, blocks, last_block_id, initial_height
                         err = "initial block can't have LastCommit signatures"
                 else:
                     full = len(jobs)
-                    jobs.append(H.CommitJob(H.MODE_FULL, chain_id, vals, state_last, hd.height - 1,
+                    jobs.append(H.CommitJob(H.MODE_FULL, chain_id, last_vals, state_last, hd.height - 1,
                                             first.last_commit))
-            late = stateful.after_commit(first, g) if stateful and err is None else None
-            out.append(hd.height)
+            late = stateful.after_commit(first, g, prev) if stateful and err is None else None
+            if dynamic and err is None and late is None:  # validateBlock passed: ApplyBlock's state transition
+                late = dynamic.transition_error(g)
+            out.append((hd.height, ids[i], hd.time))
             slots.append((light, err, full, late))
         res = check(jobs)
         return [(h, (res[light] if light is not None else None) or err or
@@ -567,21 +576,31 @@ def _replay_validated(ctx, chain_id, vals, blocks, last_block_id, initial_height
                 for h, (light, err, full, late) in zip(out, slots)]
 
     applied = 0
-    for res in in_order(range(0, len(blocks) - 1, window), run, depth):
-        for height, err in res:
+    for res in in_order(range(0, n_apply, window), run, depth):
+        for at, err in res:
+            height = at[0] if isinstance(at, tuple) else at
+            if isinstance(err, Exception):  # the reference panics in this block's transition
+                if dynamic:
+                    dynamic.last_applied = None
+                raise err
             if err is not None:
                 return applied, (height, err)
             applied += 1
+            if dynamic:
+                dynamic.last_applied = at  # (height, BlockID, time) of the block: State.Update's arguments
     return applied, None
 
 
 @dataclass
 class ReplayState:
     """The parts of state.State (internal/state/state.go) that validateBlock
-    reads, before the first block of a replay: over a static validator set
-    (Validators == NextValidators == LastValidators) and static consensus
-    params, of which (Block.MaxBytes, Block.MaxGas) are hashed and
-    Evidence.MaxBytes bounds a block's evidence."""
+    reads, before the first block of a replay.  blocksync_replay_stateful runs
+    over a static validator set (Validators == NextValidators ==
+    LastValidators) and static consensus params, of which (Block.MaxBytes,
+    Block.MaxGas) are hashed and Evidence.MaxBytes bounds a block's evidence.
+    blocksync_replay_dynamic also reads next_validators and last_validators
+    (None: `validators`), Validator.PubKeyTypes and the two heights of the last
+    change, and returns a state with all of them filled."""
     chain_id: str
     validators: H.ValidatorSet
     app_hash: bytes
@@ -595,14 +614,34 @@ class ReplayState:
     block_max_bytes: int = 22020096
     block_max_gas: int = -1
     evidence_max_bytes: int = 1048576
+    next_validators: Optional[H.ValidatorSet] = None
+    last_validators: Optional[H.ValidatorSet] = None
+    pub_key_types: List[str] = field(default_factory=lambda: ["ed25519"])
+    last_height_validators_changed: int = 1
+    last_height_consensus_params_changed: int = 1
+
+
+@dataclass
+class ConsensusParamUpdates:
+    """The parts of a tmproto.ConsensusParams update that the replay reads;
+    None: that message is absent from the update (UpdateConsensusParams,
+    types/params.go:413-469, copies a present message whole)."""
+    block: Optional[Tuple[int, int]] = None   # Block: (MaxBytes, MaxGas)
+    evidence_max_bytes: Optional[int] = None  # Evidence.MaxBytes
+    pub_key_types: Optional[List[str]] = None  # Validator.PubKeyTypes
+    version_app: Optional[int] = None         # Version.AppVersion
 
 
 @dataclass
 class BlockRecord:
     """What the application answered for one block, as SaveFinalizeBlockResponses
-    stores it: the tx results and the app hash after the block."""
+    stores it: the tx results and the app hash after the block; for
+    blocksync_replay_dynamic also the validator updates (host.ValidatorUpdate
+    or (key kind, key, power)) and the consensus-param updates."""
     results: List[H.TxResult]
     app_hash: bytes
+    validator_updates: List = field(default_factory=list)
+    consensus_param_updates: Optional[ConsensusParamUpdates] = None
 
 
 def go_time_string(t: Tuple[int, int]) -> str:
@@ -642,34 +681,51 @@ class _StatefulChecks:
         self.st, self.blocks, self.records = state, blocks, records
         self.consensus_hash = H.consensus_params_hash(state.block_max_bytes, state.block_max_gas, lib)
         self.addresses = {v.address for v in state.validators.validators}
+        self.evidence_max_bytes = state.evidence_max_bytes
 
     def window(self, ctx, lib, first_of: int, n: int) -> Tuple[int, List[bytes]]:
         """(first_of, LastResultsHash after each of blocks[first_of : first_of + n - 1]), one call."""
         lists = [self.records[j].results for j in range(first_of, first_of + n - 1)]
         return (first_of, H.results_hashes(ctx, lists, None, lib) if lists else [])
 
-    def version(self, hd) -> Optional[str]:
+    def version(self, hd, g: int = 0) -> Optional[str]:
         st = self.st
         if hd.version_app != st.version_app or hd.version_block != st.version_block:
             return "wrong Block.Header.Version. Expected {%d %d}, got {%d %d}" % (
                 st.version_block, st.version_app, hd.version_block, hd.version_app)
         return None
 
-    def app_info(self, hd, g: int, before) -> Optional[str]:
+    def app_info(self, hd, g: int, before, consensus_hash: Optional[bytes] = None) -> Optional[str]:
+        """consensus_hash: HashConsensusParams of the params in force (default: the state's)."""
         first_of, roots = before
+        if consensus_hash is None:
+            consensus_hash = self.consensus_hash
         app_hash = self.records[g - 1].app_hash if g > 0 else self.st.app_hash
         results_hash = roots[g - 1 - first_of] if g > 0 else self.st.last_results_hash
-        for name, want, got in (("AppHash", app_hash, hd.app_hash), ("ConsensusHash", self.consensus_hash, hd.consensus_hash),
+        for name, want, got in (("AppHash", app_hash, hd.app_hash), ("ConsensusHash", consensus_hash, hd.consensus_hash),
                                 ("LastResultsHash", results_hash, hd.last_results_hash)):
             if want != got:
                 return "wrong Block.Header.%s.  Expected %s, got %s" % (name, want.hex().upper(), got.hex().upper())
         return None
 
-    def after_commit(self, block, g: int) -> Optional[str]:
+    def after_commit(self, block, g: int, prev=None, addresses=None, evidence_max_bytes: Optional[int] = None
+                     ) -> Optional[str]:
+        """prev: the block before (decoded; None for the first block of the
+        replay).  addresses, evidence_max_bytes: state.Validators' addresses
+        and the bound in force (default: the state's).  Nothing is stored on
+        self: windows run on several threads."""
         st, hd = self.st, block.header
-        if hd.proposer_address not in self.addresses:
+        if addresses is None:
+            addresses = self.addresses
+        if evidence_max_bytes is None:
+            evidence_max_bytes = self.evidence_max_bytes
+        if hd.proposer_address not in addresses:
             return "block.Header.ProposerAddress %s is not a validator" % hd.proposer_address.hex().upper()
-        last_time = self.blocks[g - 1].header.time if g > 0 else st.last_block_time
+        if g > 0 and not hasattr(prev, "header"):
+            # the wire scanner handed the block before back: its own window has ended the replay there, and
+            # this answer is never read; it is an error all the same, so that nothing passes unchecked
+            return "block %d follows a block that was not handled" % hd.height
+        last_time = st.last_block_time if g == 0 else prev.header.time
         if hd.height > st.initial_height:
             if not tuple(hd.time) > tuple(last_time):
                 return "block time %s not greater than last block time %s" % (go_time_string(hd.time),
@@ -680,8 +736,8 @@ class _StatefulChecks:
         else:
             return "block height %d lower than initial height %d" % (hd.height, st.initial_height)
         got = evidence_byte_size(block.evidence)
-        if got > st.evidence_max_bytes:
-            return "Too much evidence: Max %d, got %d" % (st.evidence_max_bytes, got)
+        if got > evidence_max_bytes:
+            return "Too much evidence: Max %d, got %d" % (evidence_max_bytes, got)
         return None
 
 
@@ -721,6 +777,341 @@ def blocksync_replay_stateful(ctx, state: ReplayState, blocks: List[H.FullBlock]
                              state.initial_height, window, depth, part_size, verify_commits, lib, vals_hash,
                              state.last_block_height, "blocksync_replay_stateful",
                              _StatefulChecks(state, blocks, records, lib))
+
+
+MAX_BLOCK_SIZE_BYTES = 104857600  # types/params.go:20
+_KEY_SIZES = {H.TMV_KIND_ED25519: ("PubKeyEd25519", 32), H.TMV_KIND_SR25519: ("PubKeySr25519", 32),
+              H.TMV_KIND_SECP256K1: ("PubKeySecp256k1", 33)}
+
+
+def _update_string(u: H.ValidatorUpdate) -> str:
+    return "{%s:%s %d}" % (H.KEY_TYPE_NAMES.get(u.key_kind, "kind%d" % u.key_kind), u.pub_key.hex().upper(), u.power)
+
+
+def _key_error(u: H.ValidatorUpdate) -> Optional[str]:
+    """encoding.PubKeyFromProto's errors (crypto/encoding/codec.go:49-78)."""
+    if u.key_kind not in _KEY_SIZES:
+        return "fromproto: key type %d is not supported" % u.key_kind
+    name, size = _KEY_SIZES[u.key_kind]
+    if len(u.pub_key) != size:
+        return "invalid size for %s. Got %d, expected %d" % (name, len(u.pub_key), size)
+    return None
+
+
+def validate_validator_updates(updates: List[H.ValidatorUpdate], pub_key_types: List[str]) -> Optional[str]:
+    """validateValidatorUpdates (internal/state/execution.go:501-524).  The
+    reference prints the abci.ValidatorUpdate with %v, which renders a pointer;
+    here it prints as {<key type>:<HEX key> <power>}."""
+    for u in updates:
+        if u.power < 0:
+            return "voting power can't be negative %s" % _update_string(u)
+        if u.power == 0:
+            continue
+        err = _key_error(u)
+        if err is not None:
+            return err
+        if H.KEY_TYPE_NAMES[u.key_kind] not in pub_key_types:
+            return "validator %s is using pubkey %s, which is unsupported for consensus" % (
+                _update_string(u), H.KEY_TYPE_NAMES[u.key_kind])
+    return None
+
+
+@dataclass
+class _Params:
+    """The consensus params the replay reads."""
+    block_max_bytes: int
+    block_max_gas: int
+    evidence_max_bytes: int
+    version_app: int
+    pub_key_types: List[str]
+
+    def updated(self, u: ConsensusParamUpdates) -> "_Params":
+        """UpdateConsensusParams over these fields."""
+        p = _Params(self.block_max_bytes, self.block_max_gas, self.evidence_max_bytes, self.version_app,
+                    self.pub_key_types)
+        if u.block is not None:
+            p.block_max_bytes, p.block_max_gas = u.block
+        if u.evidence_max_bytes is not None:
+            p.evidence_max_bytes = u.evidence_max_bytes
+        if u.pub_key_types is not None:
+            p.pub_key_types = list(u.pub_key_types)
+        if u.version_app is not None:
+            p.version_app = u.version_app
+        return p
+
+    def validate(self) -> Optional[str]:
+        """ValidateConsensusParams (types/params.go:272-354) over these fields."""
+        if self.block_max_bytes <= 0:
+            return "block.MaxBytes must be greater than 0. Got %d" % self.block_max_bytes
+        if self.block_max_bytes > MAX_BLOCK_SIZE_BYTES:
+            return "block.MaxBytes is too big. %d > %d" % (self.block_max_bytes, MAX_BLOCK_SIZE_BYTES)
+        if self.block_max_gas < -1:
+            return "block.MaxGas must be greater or equal to -1. Got %d" % self.block_max_gas
+        if self.evidence_max_bytes > self.block_max_bytes:
+            return "evidence.MaxBytesEvidence is greater than upper bound, %d > %d" % (self.evidence_max_bytes,
+                                                                                      self.block_max_bytes)
+        if self.evidence_max_bytes < 0:
+            return "evidence.MaxBytes must be non negative. Got: %d" % self.evidence_max_bytes
+        if not self.pub_key_types:
+            return "len(Validator.PubKeyTypes) must be greater than 0"
+        for i, t in enumerate(self.pub_key_types):
+            if t not in H.KEY_TYPE_NAMES.values():
+                return "params.Validator.PubKeyTypes[%d], %s, is an unknown pubkey type" % (i, t)
+        return None
+
+
+class _Schedule:
+    """The validator sets and consensus params of a replay, from the state and
+    the records alone (no block is read): State.Update's part of the state,
+    for every block up to the first one whose transition fails.
+
+    With S[0], S[1], S[2] = the state's LastValidators, Validators,
+    NextValidators and S[k + 3] = IncrementProposerPriority(1) of S[k + 2]
+    updated with record k's changes, the state before block g holds
+    LastValidators = S[g], Validators = S[g + 1], NextValidators = S[g + 2]:
+    record k's updates first sign at block k + 2.  The members of a set change
+    only where a record had updates (a `version`: one list of validators that
+    every set of the version shares, so a window converts and hashes it once);
+    between two changes only the priorities and the proposer move, and one
+    validator_set_rotate call walks all of those blocks.  The whole schedule
+    is built before the first window runs; a failure or a panic of record g is
+    kept with g and comes up only when block g's own checks have passed."""
+
+    def __init__(self, state: ReplayState, records, n_blocks: int, lib):
+        self.lib = lib
+        self.first = [state.last_validators or state.validators, state.validators,
+                      state.next_validators or state.validators]
+        self.version_of: List[int] = []       # per k: which list of members S[k] holds
+        self.sets: List[H.ValidatorSet] = []  # per k: the version's validators with the proposer of S[k]
+        self.members: List[H.ValidatorSet] = []  # per version: a set to hash
+        self.base = {}                        # version -> (the set its rotation starts from, k of that set)
+        key = lambda vs: [(v.pub_key, v.key_kind, v.voting_power) for v in vs.validators]  # noqa: E731
+        for k, vs in enumerate(self.first):
+            same = [j for j in range(k) if self.first[j] is vs or key(self.first[j]) == key(vs)]
+            if same:  # the same members: one version to convert and hash, its own proposer
+                self.version_of.append(self.version_of[same[0]])
+            else:
+                self.version_of.append(len(self.members))
+                self.members.append(vs)
+            self.sets.append(H.ValidatorSet(self.members[self.version_of[k]].validators, vs.proposer_index))
+        self.base[self.version_of[2]] = (self.first[2], 2)
+        self.params = [_Params(state.block_max_bytes, state.block_max_gas, state.evidence_max_bytes, state.version_app,
+                               list(state.pub_key_types))]
+        self.vals_changed = [state.last_height_validators_changed]  # LastHeightValidatorsChanged before block g
+        self.params_changed = [state.last_height_consensus_params_changed]
+        # (g, text): block g's transition fails; (g, ValidatorSetPanic): the reference panics in it
+        self.failed: Optional[Tuple[int, object]] = None
+        height = state.last_block_height + 1 if state.last_block_height else state.initial_height
+        cur, version, pending, pending_from = self.first[2], self.version_of[2], 0, 0
+
+        def flush():  # the rotations since the last change, in one call
+            nonlocal cur, pending
+            if pending:
+                try:
+                    cur, props = H.validator_set_rotate(cur, pending, 1, lib)
+                except H.ValidatorSetPanic as e:  # a set that cannot rotate fails at its first rotation
+                    self.failed = (pending_from, e)
+                    return
+                for p in props:
+                    self.version_of.append(version)
+                    self.sets.append(H.ValidatorSet(self.members[version].validators, p))
+                pending = 0
+
+        for g in range(n_blocks):
+            rec = records[g]
+            vals_changed, params_changed, p = self.vals_changed[g], self.params_changed[g], self.params[g]
+            if rec.validator_updates:
+                ups = [u if isinstance(u, H.ValidatorUpdate) else H.ValidatorUpdate(*u) for u in rec.validator_updates]
+                err = validate_validator_updates(ups, p.pub_key_types)
+                if err is not None:
+                    self.failed = (g, "error in validator updates: " + err)
+                    break
+                err = next((e for e in map(_key_error, ups) if e is not None), None)  # PB2TM.ValidatorUpdates
+                if err is not None:
+                    self.failed = (g, err)
+                    break
+                flush()
+                if self.failed is not None:
+                    break
+                try:
+                    cur, err = H.validator_set_update(cur, ups, True, lib)
+                except H.ValidatorSetPanic as e:
+                    self.failed = (g, e)
+                    break
+                if err is not None:
+                    self.failed = (g, "commit failed for application: changing validator set: " + err)
+                    break
+                version = len(self.members)
+                self.members.append(cur)
+                self.base[version] = (cur, g + 2)
+                vals_changed = height + g + 2
+            if rec.consensus_param_updates is not None:
+                p = p.updated(rec.consensus_param_updates)
+                err = p.validate()
+                if err is not None:
+                    self.failed = (g, "commit failed for application: updating consensus params: " + err)
+                    break
+                params_changed = height + g + 1
+            if pending == 0:
+                pending_from = g
+            pending += 1  # S[g + 3]
+            self.params.append(p)
+            self.vals_changed.append(vals_changed)
+            self.params_changed.append(params_changed)
+        if self.failed is None or not isinstance(self.failed[1], H.ValidatorSetPanic):
+            flush()  # the rotations before the block that failed, or the rest of the chain
+        self.limit = self.failed[0] + 1 if self.failed else n_blocks  # the blocks whose checks run
+
+    def set_at(self, k: int) -> H.ValidatorSet:
+        """S[k] with its priorities and its proposer."""
+        if k < 3:
+            return H.ValidatorSet(list(self.first[k].validators), self.first[k].proposer_index)
+        base, born = self.base[self.version_of[k]]
+        return H.validator_set_rotate(base, k - born, 1, self.lib)[0]
+
+
+class _DynamicChecks(_StatefulChecks):
+    """_StatefulChecks against the state before each block, with the validator
+    sets and the consensus params of a _Schedule."""
+
+    def __init__(self, state: ReplayState, blocks, records, lib, set_hashes):
+        if len(records) < len(blocks) - 1:
+            raise ValueError("blocksync_replay_dynamic: %d records for %d blocks to apply"
+                             % (len(records), len(blocks) - 1))
+        self.st, self.blocks, self.records, self.lib = state, blocks, records, lib
+        self.set_hashes = set_hashes
+        self.schedule = sc = _Schedule(state, records, max(len(blocks) - 1, 0), lib)
+        self.limit = sc.limit
+        self.last_applied = None
+        # read-only from here on (the windows run on several threads): HashConsensusParams of the params
+        # before each block, and the addresses of each distinct set
+        hashes: Dict[Tuple[int, int], bytes] = {}
+        for p in sc.params:
+            key = (p.block_max_bytes, p.block_max_gas)
+            if key not in hashes:
+                hashes[key] = H.consensus_params_hash(key[0], key[1], lib)
+        self._consensus_hash = [hashes[(p.block_max_bytes, p.block_max_gas)] for p in sc.params]
+        self._addresses = [frozenset(x.address for x in vs.validators) for vs in sc.members]
+
+    def window(self, ctx, lib, first_of: int, n: int):
+        """_StatefulChecks.window, and the hash of every distinct validator set
+        that the window's blocks name, from one set_hashes call."""
+        sc = self.schedule
+        versions = sorted({sc.version_of[k] for k in range(first_of + 1, first_of + n + 2)})
+        hashes = self.set_hashes([sc.members[v] for v in versions])
+        return _StatefulChecks.window(self, ctx, lib, first_of, n) + (dict(zip(versions, hashes)),)
+
+    def sets(self, g: int, before):
+        sc, hashes = self.schedule, before[2]
+        return sc.sets[g], sc.sets[g + 1], hashes[sc.version_of[g + 1]], hashes[sc.version_of[g + 2]]
+
+    def version(self, hd, g: int = 0) -> Optional[str]:
+        app = self.schedule.params[g].version_app
+        if hd.version_app != app or hd.version_block != self.st.version_block:
+            return "wrong Block.Header.Version. Expected {%d %d}, got {%d %d}" % (
+                self.st.version_block, app, hd.version_block, hd.version_app)
+        return None
+
+    def app_info(self, hd, g: int, before) -> Optional[str]:
+        return _StatefulChecks.app_info(self, hd, g, before[:2], self._consensus_hash[g])
+
+    def after_commit(self, block, g: int, prev=None) -> Optional[str]:
+        sc = self.schedule
+        return _StatefulChecks.after_commit(self, block, g, prev, self._addresses[sc.version_of[g + 1]],
+                                            sc.params[g].evidence_max_bytes)
+
+    def transition_error(self, g: int) -> Optional[str]:
+        f = self.schedule.failed
+        return f[1] if f is not None and f[0] == g else None
+
+    def state_after(self, applied: int, ctx) -> ReplayState:
+        """The state after `applied` blocks (State.Update's result, with the
+        AppHash that state.Save fills in)."""
+        import dataclasses
+        sc, st = self.schedule, self.st
+        p = sc.params[applied]
+        out = dataclasses.replace(
+            st, last_validators=sc.set_at(applied), validators=sc.set_at(applied + 1),
+            next_validators=sc.set_at(applied + 2), block_max_bytes=p.block_max_bytes, block_max_gas=p.block_max_gas,
+            evidence_max_bytes=p.evidence_max_bytes, version_app=p.version_app, pub_key_types=list(p.pub_key_types),
+            last_height_validators_changed=sc.vals_changed[applied],
+            last_height_consensus_params_changed=sc.params_changed[applied],
+            last_block_id=st.last_block_id or H.BlockID())
+        if applied:
+            height, block_id, time = self.last_applied
+            rec = self.records[applied - 1]
+            out = dataclasses.replace(out, last_block_height=height, last_block_id=block_id, last_block_time=tuple(time),
+                                      app_hash=rec.app_hash,
+                                      last_results_hash=H.results_hashes(ctx, [rec.results], None, self.lib)[0])
+        return out
+
+
+def mixed_set_hashes(ctx, sets: List[H.ValidatorSet], lib=None) -> List[bytes]:
+    """ValidatorSet.Hash of each set: one validator_set_hashes call on the
+    device over the sets of ed25519 and sr25519 keys; a set that holds a
+    secp256k1 key (tmv_validator_set_hashes does not take those), and every
+    set without a context, on the host (host.validator_set_hash_host)."""
+    dev = [i for i, vs in enumerate(sets) if ctx is not None and all(
+        v.key_kind in (H.TMV_KIND_ED25519, H.TMV_KIND_SR25519) and len(v.pub_key) == 32 for v in vs.validators)]
+    out: List[Optional[bytes]] = [None] * len(sets)
+    if dev:
+        for i, h in zip(dev, validator_set_hashes(ctx, [sets[i] for i in dev])):
+            out[i] = h
+    return [h if h is not None else H.validator_set_hash_host(vs, lib) for h, vs in zip(out, sets)]
+
+
+def blocksync_replay_dynamic(ctx, state: ReplayState, blocks, records: List[BlockRecord], window: int = 600,
+                             depth: Optional[int] = None, part_size: int = 65536, verify_commits=None,
+                             set_hashes=None, lib=None, wire: bool = False
+                             ) -> Tuple[int, Optional[Tuple[int, str]], ReplayState]:
+    """blocksync_replay_stateful across validator-set and consensus-param
+    changes: the reference's ApplyBlock loop with State.Update
+    (internal/state/execution.go:527-595) between the blocks.  blocks: the
+    FullBlocks, or with wire=True their protobuf bytes (the window of
+    blocksync_replay_wire).  records[i]: what the application answered for
+    blocks[i], with its validator_updates and consensus_param_updates.
+
+    Block g is checked against the state before it -- VerifyCommitLight of the
+    pair by state.Validators, ValidatorsHash against state.Validators.Hash(),
+    NextValidatorsHash against state.NextValidators.Hash(), LastCommit by
+    state.LastValidators.VerifyCommit, the proposer by state.Validators, the
+    version, ConsensusHash and the evidence bound by the params in force --
+    with blocksync_replay_stateful's texts in its order.  Then the transition,
+    whose failure ends the replay at g's height with g not applied:
+      error in validator updates: voting power can't be negative {T:K P}
+      error in validator updates: validator {T:K P} is using pubkey T, which is unsupported for consensus
+      error in validator updates: invalid size for PubKeyEd25519. Got %d, expected %d   (and the other key types)
+      commit failed for application: changing validator set: <UpdateWithChangeSet's text>
+      commit failed for application: updating consensus params: <ValidateConsensusParams' text>
+    The reference prints an abci.ValidatorUpdate with %v, which renders a
+    pointer; here {T:K P} is {<key type>:<HEX key> <power>}.
+    UpdateConsensusParams and ValidateConsensusParams cover the fields of
+    ConsensusParamUpdates (block, evidence max bytes, pub key types, app
+    version).  Updates of block h change NextValidators after h and first sign
+    at h + 2; param updates hold from h + 1.  A change set on which the
+    reference panics raises host.ValidatorSetPanic, once the replay has reached
+    the block whose transition it belongs to (an earlier block that fails a
+    check ends the replay with its own error first).
+
+    The validator sets and params of every block follow from the state and the
+    records alone (host.validator_set_update / validator_set_rotate, on the
+    host), so the windows stay independent and `depth` of them are in flight.
+    Per window: one `set_hashes` call (sets -> hashes; default
+    mixed_set_hashes) over the window's distinct sets -- a set is new only
+    where a record had updates -- and one commit batch (`verify_commits`).
+    Not done here: evidence verification, vote extensions, the synchrony,
+    timeout and ABCI params, LoadValidators' checkpoint rotation.
+
+    Returns (blocks applied, (height, error) or None, the state after the
+    applied blocks: the three validator sets with their priorities and
+    proposers, the params, the heights of the last changes)."""
+    if set_hashes is None:
+        set_hashes = lambda sets: mixed_set_hashes(ctx, sets, lib)  # noqa: E731
+    dyn = _DynamicChecks(state, blocks, records, lib, set_hashes)
+    applied, err = _replay_validated(ctx, state.chain_id, None, blocks, state.last_block_id or H.BlockID(),
+                                     state.initial_height, window, depth, part_size, verify_commits, lib, None,
+                                     state.last_block_height, "blocksync_replay_dynamic", dyn, wire)
+    return applied, err, dyn.state_after(applied, ctx)
 
 
 # ---- merkle proofs: Txs.Hash / Txs.Proof (types/tx.go:30-75) ----

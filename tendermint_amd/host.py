@@ -383,7 +383,9 @@ class PreparedJobs:
         for j, jb in enumerate(jobs):
             cv, nv, prop = None, 0, -1
             if jb.vals is not None:
-                key = id(jb.vals)
+                # sets that share one list of validators (a replay's sets between two validator
+                # changes: only the proposer moves) share one tmv_validator array
+                key = id(jb.vals.validators) if type(jb.vals) is ValidatorSet else id(jb.vals)
                 if key not in vcache:
                     vcache[key] = _c_validators(k, jb.vals)
                 cv, nv, prop = vcache[key], len(jb.vals.validators), jb.vals.proposer_index
@@ -1749,3 +1751,184 @@ def consensus_params_verify(ctx, items: List[ConsensusParamsResult], lib=None) -
     if rc < 0:
         raise NativeError(f"tmv_consensus_params_verify failed ({rc})")
     return _texts(results, errs, n)
+
+
+# ---- validator-set updates (include/tmhost.h: tmv_validator_set_update / _new / _rotate / _hash_host) ----
+# types/validator_set.go:70-234, 362-650 on the host, no engine: what State.Update does to NextValidators.
+
+VALSET_OK, VALSET_ERROR, VALSET_PANIC = 0, 1, 2
+KEY_TYPE_NAMES = {TMV_KIND_ED25519: "ed25519", TMV_KIND_SR25519: "sr25519", TMV_KIND_SECP256K1: "secp256k1"}
+
+
+class ValidatorSetPanic(Exception):
+    """The reference panics here (TMV_VALSET_PANIC); the text is the panic's."""
+
+
+@dataclass
+class ValidatorUpdate:
+    """abci.ValidatorUpdate: the key and the new power (0 removes the validator)."""
+    key_kind: int
+    pub_key: bytes
+    power: int
+
+
+class CValidatorUpdate(ctypes.Structure):
+    _fields_ = [("key_kind", ctypes.c_uint8), ("pub_key", _u8p), ("pub_key_len", ctypes.c_uint32),
+                ("power", ctypes.c_int64)]
+
+
+def _setup_valset(L):
+    if not getattr(L, "_tmhost_valset", False):
+        vp, up = ctypes.POINTER(CValidator), ctypes.POINTER(CValidatorUpdate)
+        u32p, i32p = ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int32)
+        L.tmv_validator_set_update.argtypes = [vp, ctypes.c_uint32, up, ctypes.c_uint32, ctypes.c_int, _u8p, vp,
+                                               ctypes.c_uint32, u32p, ctypes.c_char_p, ctypes.c_size_t]
+        L.tmv_validator_set_new.argtypes = [up, ctypes.c_uint32, _u8p, vp, ctypes.c_uint32, u32p, i32p,
+                                            ctypes.c_char_p, ctypes.c_size_t]
+        L.tmv_validator_set_rotate.argtypes = [vp, ctypes.c_uint32, ctypes.c_int32, ctypes.c_uint32, i32p,
+                                               ctypes.c_char_p, ctypes.c_size_t]
+        L.tmv_validator_set_hash_host.argtypes = [vp, ctypes.c_uint32, _u8p]
+        L._tmhost_valset = True
+    return L
+
+
+def _valset_array(k: _Keep, vals: ValidatorSet):
+    """(numpy tmv_validator[], pointer -> the bytes object it points to) for a set."""
+    _c_validators(k, vals)
+    a = k.refs[-1]
+    n = len(vals.validators)
+    back = dict(zip(a["address"][:n].tolist(), (v.address for v in vals.validators)))
+    back.update(zip(a["pub_key"][:n].tolist(), (v.pub_key for v in vals.validators)))
+    return a, back
+
+
+def _c_updates(k: _Keep, updates):
+    import numpy as np
+    ups = [u if isinstance(u, ValidatorUpdate) else ValidatorUpdate(*u) for u in updates]
+    a = np.zeros(max(1, len(ups)), dtype=_dt("vu", CValidatorUpdate))
+    back = {}
+    if ups:
+        n = len(ups)
+        a["pub_key"][:n], a["pub_key_len"][:n] = _blob_ptrs(k, [u.pub_key for u in ups])
+        a["key_kind"][:n] = [u.key_kind for u in ups]
+        a["power"][:n] = [u.power for u in ups]
+        back = dict(zip(a["pub_key"][:n].tolist(), (u.pub_key for u in ups)))
+    k.refs.append(a)
+    return a, len(ups), back
+
+
+def _valset_result(rc: int, err, what: str) -> Optional[str]:
+    if rc == VALSET_OK:
+        return None
+    text = err.value.decode(errors="replace")
+    if rc == VALSET_ERROR:
+        return text
+    if rc == VALSET_PANIC:
+        raise ValidatorSetPanic(text)
+    raise NativeError(f"{what} failed ({rc})")
+
+
+def _py_valset(out, n: int, back, scratch, proposer_index: int = -1) -> ValidatorSet:
+    """The output array of a set call: keys and addresses by the pointers they
+    borrow (an input's bytes object, or 20 bytes of the address scratch)."""
+    base = ctypes.addressof(scratch) if scratch is not None else 0
+    raw = bytes(scratch) if scratch is not None else b""
+
+    def take(p):
+        b = back.get(p)
+        if b is None:
+            b = back[p] = raw[p - base:p - base + 20] if p else b""
+        return b
+    return ValidatorSet([Validator(take(ap), take(kp), pw, kk, pr) for ap, kp, pw, kk, pr in zip(
+        out["address"][:n].tolist(), out["pub_key"][:n].tolist(), out["voting_power"][:n].tolist(),
+        out["key_kind"][:n].tolist(), out["proposer_priority"][:n].tolist())], proposer_index)
+
+
+def validator_set_update(vals: ValidatorSet, updates, allow_deletes: bool = True, lib=None
+                         ) -> Tuple[Optional[ValidatorSet], Optional[str]]:
+    """ValidatorSet.UpdateWithChangeSet (types/validator_set.go:584-650) on a
+    copy: (the new set, None) or (None, the reference's error text); a
+    ValidatorSetPanic where the reference panics.  updates: ValidatorUpdate or
+    (key kind, key, power); the address follows from the key as NewValidator
+    derives it.  The new set's proposer_index is -1: State.Update goes on to
+    IncrementProposerPriority(1) (validator_set_rotate)."""
+    import numpy as np
+    L = _setup_valset(lib or _native.lib())
+    k = _Keep()
+    a, back = _valset_array(k, vals)
+    u, nu, uback = _c_updates(k, updates)
+    back.update(uback)
+    nv = len(vals.validators)
+    scratch = (ctypes.c_uint8 * max(1, 20 * nu))()
+    out = np.zeros(max(1, nv + nu), dtype=_dt("v", CValidator))
+    n_out = ctypes.c_uint32(0)
+    err = ctypes.create_string_buffer(4096)
+    vp, up = ctypes.POINTER(CValidator), ctypes.POINTER(CValidatorUpdate)
+    rc = L.tmv_validator_set_update(ctypes.cast(a.ctypes.data, vp), nv, ctypes.cast(u.ctypes.data, up), nu,
+                                    1 if allow_deletes else 0, ctypes.cast(scratch, _u8p),
+                                    ctypes.cast(out.ctypes.data, vp), nv + nu, ctypes.byref(n_out), err, len(err))
+    text = _valset_result(rc, err, "tmv_validator_set_update")
+    if text is not None:
+        return None, text
+    return _py_valset(out, n_out.value, back, scratch), None
+
+
+def new_validator_set(validators, lib=None) -> ValidatorSet:
+    """NewValidatorSet (types/validator_set.go:70-80) over (key kind, key,
+    power) entries: the set in set order with the priorities and the proposer
+    of its first election.  The reference panics on a change set that fails:
+    a ValidatorSetPanic with "cannot create validator set: ..."."""
+    import numpy as np
+    L = _setup_valset(lib or _native.lib())
+    k = _Keep()
+    u, nu, back = _c_updates(k, validators)
+    scratch = (ctypes.c_uint8 * max(1, 20 * nu))()
+    out = np.zeros(max(1, nu), dtype=_dt("v", CValidator))
+    n_out, prop = ctypes.c_uint32(0), ctypes.c_int32(-1)
+    err = ctypes.create_string_buffer(4096)
+    vp, up = ctypes.POINTER(CValidator), ctypes.POINTER(CValidatorUpdate)
+    rc = L.tmv_validator_set_new(ctypes.cast(u.ctypes.data, up), nu, ctypes.cast(scratch, _u8p),
+                                 ctypes.cast(out.ctypes.data, vp), nu, ctypes.byref(n_out), ctypes.byref(prop), err,
+                                 len(err))
+    text = _valset_result(rc, err, "tmv_validator_set_new")
+    if text is not None:  # the change set's errors are panics here
+        raise ValidatorSetPanic(text)
+    return _py_valset(out, n_out.value, back, scratch, prop.value)
+
+
+def validator_set_rotate(vals: ValidatorSet, steps: int = 1, times: int = 1, lib=None
+                         ) -> Tuple[ValidatorSet, List[int]]:
+    """`steps` successive IncrementProposerPriority(times) calls
+    (types/validator_set.go:116-138) on a copy, as State.Update makes one per
+    block with times = 1: (the set after the last call, the proposer's index
+    after each call).  One call with times = k is not k calls with times = 1:
+    the reference rescales and centres the priorities once per call."""
+    L = _setup_valset(lib or _native.lib())
+    k = _Keep()
+    _c_validators(k, vals)
+    a = k.refs[-1]
+    n = len(vals.validators)
+    props = (ctypes.c_int32 * max(1, steps))()
+    err = ctypes.create_string_buffer(4096)
+    rc = L.tmv_validator_set_rotate(ctypes.cast(a.ctypes.data, ctypes.POINTER(CValidator)), n, times, steps, props,
+                                    err, len(err))
+    text = _valset_result(rc, err, "tmv_validator_set_rotate")
+    if text is not None:
+        raise NativeError("tmv_validator_set_rotate: " + text)
+    prios = a["proposer_priority"][:n].tolist()
+    after = ValidatorSet([Validator(v.address, v.pub_key, v.voting_power, v.key_kind, p)
+                          for v, p in zip(vals.validators, prios)], props[steps - 1] if steps else vals.proposer_index)
+    return after, list(props[:steps])
+
+
+def validator_set_hash_host(vals: ValidatorSet, lib=None) -> bytes:
+    """ValidatorSet.Hash on the host (tmv_validator_set_hash_host): for the
+    sets that hold secp256k1 keys, which the device call does not take."""
+    L = _setup_valset(lib or _native.lib())
+    k = _Keep()
+    cv = _c_validators(k, vals)
+    out = (ctypes.c_uint8 * 32)()
+    rc = L.tmv_validator_set_hash_host(cv, len(vals.validators), ctypes.cast(out, _u8p))
+    if rc < 0:
+        raise NativeError(f"tmv_validator_set_hash_host failed ({rc})")
+    return bytes(out)
